@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- PCG iterations/s of the Gauss-Newton solve of image_warping 4096^2 (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--size 4096]
+    python bench.py --gpus N --steps K --warmup W [--size 4096] [--dump-outputs DIR] [--full]
 
 A "step" is one Opt_ProblemStep: one Gauss-Newton iteration = evalJTF + `lIterations` (400, the reference's
 examples/image_warping/src/main.cpp:113-114) matrix-free PCG iterations + update + cost.
@@ -13,7 +13,12 @@ ghost rows; per PCG iteration the ranks all-reduce four doubles (peer-mapped mai
 OPT_AMD_COMM=rccl) and every 7th iteration exchange 8 edge rows of r and p with each slab neighbour -- total work fixed => "strong" scaling.
 `--size 8192` is BASELINE config 5.
 
-The same JSON line carries
+A plain run sets up, warms up, times the K steps and prints one JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step)
+and the workload's costs before the first and after the last step.  --dump-outputs DIR additionally writes what the last timed step left in the unknowns
+(DIR/offset.npy, DIR/angle.npy at a fixed seeded sample of DIR/pixel_index.npy, DIR/cost.npy; float32 / float64, < 64 MB) -- the inputs are the same
+in every run with the same arguments, so two builds can be compared output for output.
+
+With --full the same JSON line also carries
   roofline     : the dominant kernel (`PCGIteration`: ONE launch per PCG iteration doing the work of the reference's PCGStep1 + PCGStep2 +
                  PCGStep3) timed with hipEvents on the solver's stream.  `achieved` = the bytes the kernel has to move (its own byte model,
                  53 B/pixel: the last two search directions in, the new one out, angle, flags, delta every second launch -- DESIGN.md section 3.1) / average launch time,
@@ -27,7 +32,7 @@ The same JSON line carries
                  memory) on the same workload: PCG iterations/s, per-kernel times, `frac` against the reference formulation's 180 B/pixel and `frac_physical` against the 168.8 it
                  moves (PMC-measured), relative error per step against the frozen exact-order oracle builds -- what parity at the contract costs.
   smoke        : N > 1 only: a Gauss-Newton step of 12 PCG iterations through the real kernels on every rank BEFORE the timed region, verdict collective; a peer communicator
-                 that fails it is replaced by RCCL on every rank and the line says so.
+                 that fails it is replaced by RCCL on every rank and the line says so  (Part of setting up the communicator: a plain run does it too.)
   cpu_baseline : the CPU oracle (a port, not the reference) timed on a bounded sample on the host cores (rank 0, N = 1 only).
   parity       : cost after the first step next to the frozen oracle value for this workload (tests/golden/bench_costs.json).
   box          : what the line ran on -- power cap, clocks and power sampled under load, the box's own measured copy bandwidth (boxes of the pool differ by ~10 %).
@@ -81,7 +86,32 @@ def parse():
     ap.add_argument("--dry", action="store_true", help="set everything up (slabs, communicator, plan) and print, per rank, what the solve WOULD do -- on chip or one launch per "
                                                        "iteration, communicator and its fast paths, ghost depth, bytes per exchange (OptAmd_PlanDescribe) -- without running a step")
     ap.add_argument("--share-gpu", action="store_true", help="functional check of the N-rank path on a 1-GPU box: all ranks use device 0, set-up over gloo (timings meaningless)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check everything else: roofline leg, parity against the frozen oracle, the metric's "
+                                                        "whole solve, general UrShape, on-chip table, example flows, contract loop, box, CPU baseline, RCCL leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (unknowns at a fixed seeded sample of pixels, cost) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_PIXELS = 1 << 21        # sampled pixels of --dump-outputs: 2 M x (offset 8 + angle 4 + index 8 B) = 40 MB
+DUMP_NAMES = {0: "offset", 1: "angle"}      # image_warping's unknowns by binding slot
+
+
+def dump_index(n_pixels):
+    """Flat pixel indices that --dump-outputs writes: all of them, or a fixed seeded sample of DUMP_PIXELS in increasing order."""
+    import numpy as np
+    if n_pixels <= DUMP_PIXELS:
+        return np.arange(n_pixels, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n_pixels, DUMP_PIXELS, replace=False))
+
+
+def dump_outputs(out_dir, arrays, cost):
+    """arrays: {name: numpy array}; written with the index and the cost as float32 / float64 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    np.save(os.path.join(out_dir, "cost.npy"), np.array([cost], dtype=np.float64))
 
 
 def free_port():
@@ -467,7 +497,7 @@ def main():
         dev = api.to_device(P)
         host0, unknown_slots = P.params, P.unknown_slots
         solver = api.Solver(api.energy_file("image_warping"), "gaussNewtonGPU", (W, H))
-    extra_steps = 0 if args.no_extras else 2      # the roofline leg runs on the SAME plan, after the timed steps (per-kernel hipEvents switched on by OptAmd_PlanSetTiming)
+    extra_steps = 2 if (args.full and not args.no_extras) else 0      # the roofline leg runs on the SAME plan, after the timed steps (per-kernel hipEvents switched on by OptAmd_PlanSetTiming)
     solver.set_parameter("nIterations", total_steps + extra_steps)
     solver.set_parameter("lIterations", args.liters)
 
@@ -584,7 +614,23 @@ def main():
     if err:
         fail(err, "timed steps")
 
-    gold, env = golden_cost(W, args.liters)
+    # ---- --dump-outputs: the unknowns as the last timed step left them, at the sampled pixels (each rank reads the sampled pixels of the rows it owns) ----
+    if args.dump_outputs:
+        import numpy as np
+        idx = dump_index(W * H)
+        row0, rows, ghost = (job.layout.row0, job.layout.rows, job.layout.ghost) if distributed else (0, H, 0)
+        mine = idx[(idx >= row0 * W) & (idx < (row0 + rows) * W)]
+        local = torch.from_numpy(mine - (row0 - ghost) * W).to(dev[unknown_slots[0]].device)
+        parts = {DUMP_NAMES.get(slot, f"unknown{slot}"): dev[slot].reshape(dev[slot].shape[0] * W, -1)[local].squeeze(-1).cpu().numpy() for slot in unknown_slots}
+        if distributed:
+            allp = [None] * world
+            dist.all_gather_object(allp, parts)
+            parts = {k: np.concatenate([p[k] for p in allp]) for k in parts}
+        if rank == 0:
+            parts["pixel_index"] = idx.astype(np.float64)
+            dump_outputs(args.dump_outputs, parts, cost_final)
+
+    gold, env = golden_cost(W, args.liters) if args.full else (None, None)
     parity = None
     if gold is not None and len(costs) >= 2:
         n = min(len(costs), len(gold))
@@ -605,7 +651,7 @@ def main():
 
     # ---- roofline leg: the same plan goes on for two more steps with per-kernel hipEvents on the solver's stream -------------------
     roofline = None
-    sha = kernel_src_sha16()
+    sha = kernel_src_sha16() if args.full else None
     comm_us = None
     if extra_steps:
         # single GPU: one event pair per RUN of launches of one name -- the 400 PCGIteration launches of a step cost two event records, not 800.  Row slabs: a pair per
@@ -677,7 +723,7 @@ def main():
 
     # ---- the metric's own solve: Opt_ProblemSolve, 8 Gauss-Newton steps x 400 PCG iterations from the initial guess (main.cpp:113-114), timed as a whole ----
     solve = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for slot in unknown_slots:
             dev[slot].copy_(torch.from_numpy(host0[slot]))
         solver.set_parameter("nIterations", 8)
@@ -737,7 +783,7 @@ def main():
 
     # ---- the general kernel (arbitrary UrShape: + U, 61 B/pixel; M_a rebuilt from the pairs the stencil evaluates) on the same input ------
     general = None
-    if not distributed and not args.no_extras:
+    if args.full and not distributed and not args.no_extras:
         solver.close()
         del dev
         os.environ["OPT_AMD_LATTICE"] = "0"
@@ -761,16 +807,16 @@ def main():
     # ---- the on-chip linear solve (opt_amd/csrc/iw_onchip.h) at the sizes it exists for, against the streaming loop on the same box ---------------------
     onchip = None
     flows = None
-    if not distributed and not args.no_extras:
+    if args.full and not distributed and not args.no_extras:
         onchip = onchip_table(api, wl, torch, args.liters)
         flows = reference_example_flows()
         if flows is not None:
             flows["parity_vs_frozen_reference_runs"] = flow_parity(flows)
     contract = None
-    if not distributed and not args.no_extras:
+    if args.full and not distributed and not args.no_extras:
         contract = contract_loop_leg(api, wl, torch, W, H, args.liters)
         contract["headline_over_contract_loop"] = value / contract["pcg_iters_per_s"]
-    box = box_info(torch) if (rank == 0 and not args.share_gpu) else None
+    box = box_info(torch) if (args.full and rank == 0 and not args.share_gpu) else None
     if box and roofline and box.get("copy_gbs_float4"):
         best = max(box["copy_gbs_float4"], box["copy_gbs_float4_nontemporal"])
         roofline["frac_of_box_copy_float4"] = (roofline.get("hbm_achieved") or roofline["achieved"]) / best
@@ -779,13 +825,13 @@ def main():
 
     # ---- CPU leg last: the GPU work sits at the front of the run in one block ------------------------------------------------------------
     cpu = None
-    if rank == 0 and not distributed and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not distributed and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_size, args.cpu_liters)
 
     # ---- the same slabs over RCCL (north_star names RCCL over xGMI): a short leg in the same job, so that RCCL demonstrably sees N ranks and both per-iteration
     # times stand side by side.  Ranks that share one GPU cannot form an RCCL communicator.
     rccl_leg = None
-    if distributed and args.comm == "peer" and not args.no_extras:
+    if args.full and distributed and args.comm == "peer" and not args.no_extras:
         if args.share_gpu:
             rccl_leg = {"skipped": "needs distinct devices (ranks share one GPU in this run)"}
         else:
@@ -814,10 +860,12 @@ def main():
                                       "(synthetic cat512-style constraints, border pinned)",
                           "parallelism": f"row-slabs x{world}, comm={args.comm}, ranks in the communicator: {comm_ranks}" if distributed else "single GPU",
                           "step": "one Opt_ProblemStep (1 GN iteration)"},
-               "gn_solve": solve, "gn_solve_ms": solve["gn_solve_ms"] if solve else None,
-               "cost_initial": costs[0], "cost_final": cost_final, "parity": parity, "comm_ranks": comm_ranks, "preflight": preflight, "smoke": smoke, "rccl_leg": rccl_leg,
-               "per_iteration_ms": dt / args.steps / args.liters * 1e3,
-               "kernel_src_sha16": sha, "box": box, "roofline": roofline, "contract_loop": contract, "general_urshape": general, "onchip": onchip, "reference_example_flows": flows, "cpu_baseline": cpu}
+               "cost_initial": costs[0], "cost_final": cost_final, "comm_ranks": comm_ranks, "preflight": preflight, "smoke": smoke,
+               "per_iteration_ms": dt / args.steps / args.liters * 1e3}
+        if args.full:
+            out.update({"gn_solve": solve, "gn_solve_ms": solve["gn_solve_ms"] if solve else None, "parity": parity, "rccl_leg": rccl_leg,
+                        "kernel_src_sha16": sha, "box": box, "roofline": roofline, "contract_loop": contract, "general_urshape": general, "onchip": onchip,
+                        "reference_example_flows": flows, "cpu_baseline": cpu})
         print(json.dumps(out))
     if distributed:
         job.close()

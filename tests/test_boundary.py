@@ -202,3 +202,23 @@ def test_bench_helpers_without_a_gpu():
     assert bench.measured_traffic("0" * 16) == (None, None)
     costs, env = bench.golden_cost(4096, 400)
     assert costs is not None and len(costs) == 3 and env is not None and env[0] == 0.0
+
+
+def test_bench_dump_sample_is_fixed_and_small(tmp_path):
+    """bench.py --dump-outputs: the sampled pixels are the same in every run, strictly increasing, all of them for small images, and the files of the
+    largest size the bench takes stay under 64 MB, float32 / float64 only."""
+    import importlib
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    assert np.array_equal(bench.dump_index(512 * 512), np.arange(512 * 512))
+    a, b = bench.dump_index(4096 * 4096), bench.dump_index(4096 * 4096)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_PIXELS and np.all(np.diff(a) > 0) and a[-1] < 4096 * 4096
+    n = bench.DUMP_PIXELS
+    bench.dump_outputs(str(tmp_path), {"offset": np.zeros((n, 2), np.float32), "angle": np.zeros(n, np.float32), "pixel_index": bench.dump_index(8192 * 8192).astype(np.float64)}, 1.5)
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["angle.npy", "cost.npy", "offset.npy", "pixel_index.npy"]
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) < 64 << 20
+    assert all(np.load(os.path.join(tmp_path, f)).dtype in (np.float32, np.float64) for f in files)
+    assert np.load(os.path.join(tmp_path, "cost.npy"))[0] == 1.5

@@ -394,3 +394,36 @@ def test_timing_can_be_switched_on_between_steps():
     assert g.kernel_timings().get("PCGIteration", (0, 0.0))[0] == 0        # totals restart when the switch is flipped
     g.close()
     assert got == want[:3]
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (no --full): the line carries the headline and ms_per_step and none of the --full legs, and DIR holds
+    the unknowns after the last timed step at the sampled pixels -- the same as an in-process Init + W + K Opt_ProblemSteps of the same workload."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W = 512
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--size", str(W), "--steps", "2", "--warmup", "1", "--liters", "20", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and abs(out["value"] - 20 * 1e3 / out["ms_per_step"]) <= 1e-6 * out["value"]
+    for k in ("roofline", "box", "cpu_baseline", "parity", "gn_solve", "contract_loop", "onchip", "general_urshape", "reference_example_flows"):
+        assert k not in out, k
+    idx = np.load(tmp_path / "pixel_index.npy").astype(np.int64)
+    off, ang, cost = np.load(tmp_path / "offset.npy"), np.load(tmp_path / "angle.npy"), np.load(tmp_path / "cost.npy")
+    assert off.dtype == np.float32 and off.shape == (len(idx), 2) and ang.shape == (len(idx),) and cost[0] == out["cost_final"]
+    P = wl.image_warping(W, W)
+    dev = api.to_device(P)
+    s = api.Solver(api.energy_file("image_warping"), "gaussNewtonGPU", (W, W))
+    s.set_parameter("nIterations", 3); s.set_parameter("lIterations", 20)
+    s.init(dev)
+    for _ in range(3):
+        s.step(dev)
+    assert abs(s.cost() - cost[0]) <= 1e-5 * abs(cost[0])
+    assert rel_err(off, dev[0].reshape(-1, 2).cpu().numpy()[idx]) < 1e-5 and rel_err(ang, dev[1].reshape(-1).cpu().numpy()[idx]) < 1e-5
+    s.close()

@@ -1,13 +1,28 @@
-"""CPU tests of the input-format readers (opt_amd/io.py).  The round trips always run; the checks against the
-reference's own fixture files run only where /root/reference exists (never on the GPU box)."""
+"""CPU tests of the input-format readers (opt_amd/io.py): round trips, and the reference's own example inputs (examples/data: cat512.constraints and the
+shape_from_shading `default` set), stored under tests/golden/reference_data (tests/golden/make_reference_fixtures.py; the 640x480 imagedumps xz-compressed)."""
+import lzma
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 from opt_amd import io, workloads as wl
 
-REF = "/root/reference/examples/data"
+GOLDEN_REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
+
+
+@pytest.fixture(scope="module")
+def ref_data(tmp_path_factory):
+    """The reference's examples/data layout, rebuilt byte for byte from the stored fixtures."""
+    d = tmp_path_factory.mktemp("reference_data")
+    shutil.copytree(GOLDEN_REF, str(d), dirs_exist_ok=True)
+    sfs = os.path.join(str(d), "shape_from_shading")
+    for f in os.listdir(sfs):
+        if f.endswith(".xz"):
+            with lzma.open(os.path.join(sfs, f)) as src, open(os.path.join(sfs, f[:-3]), "wb") as dst:
+                dst.write(src.read())
+    return str(d)
 
 
 def test_imagedump_roundtrip(tmp_path):
@@ -40,22 +55,20 @@ def test_constraints_reader(tmp_path):
     assert io.read_constraints(tmp_path / "c.constraints") == [(30, 132, 59, 44), (229, 51, 157, 91)]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present (GPU box)")
-def test_reference_fixtures_decode_as_documented():
-    assert io.read_constraints(os.path.join(REF, "cat512.constraints")) == wl.CAT512_MARKERS
-    p = io.read_sfs_parameters(os.path.join(REF, "shape_from_shading", "default.SFSSolverParameters"))
+def test_reference_fixtures_decode_as_documented(ref_data):
+    assert io.read_constraints(os.path.join(ref_data, "cat512.constraints")) == wl.CAT512_MARKERS
+    p = io.read_sfs_parameters(os.path.join(ref_data, "shape_from_shading", "default.SFSSolverParameters"))
     fx = wl.SFS_FIXTURE
     assert abs(p["weightFitting"] - fx["w_p"]) < 1e-4 and abs(p["weightRegularizer"] - fx["w_s"]) < 1e-4 and abs(p["weightShading"] - fx["w_g"]) < 1e-4
     assert abs(p["fx"] - fx["fx"]) < 1e-3 and abs(p["ux"] - fx["ux"]) < 1e-3
     np.testing.assert_allclose(p["lightingCoefficients"], fx["L"], atol=1e-4)
-    P = io.load_sfs_example(os.path.join(REF, "shape_from_shading", "default"))
+    P = io.load_sfs_example(os.path.join(ref_data, "shape_from_shading", "default"))
     assert P.dims == (640, 480) and P.params[16].shape == (480, 640) and P.params[19].dtype == np.uint8
     assert int((P.params[17] > 0).sum()) == 640 * 480 - 115038          # 115 038 invalid depths
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present (GPU box)")
-def test_oracle_runs_on_the_reference_sfs_fixture(oracle_lib):
-    P = io.load_sfs_example(os.path.join(REF, "shape_from_shading", "default"))
+def test_oracle_runs_on_the_reference_sfs_fixture(oracle_lib, ref_data):
+    P = io.load_sfs_example(os.path.join(ref_data, "shape_from_shading", "default"))
     o = oracle_lib.OracleSolver("shape_from_shading", "LMGPU", True, P.dims)
     o.set("nIterations", 2); o.set("lIterations", 5)
     o.init(P.params); c0 = o.cost()

@@ -30,7 +30,7 @@ python bench.py --dry > $out/dry_1.json 2> $out/dry_1.err
 timeout 300 python bench.py --gpus 8 --share-gpu --dry > $out/dry_8_4096.json 2> $out/dry_8_4096.err
 timeout 300 python bench.py --gpus 2 --share-gpu --dry > $out/dry_2_4096.json 2> $out/dry_2_4096.err
 # the N-rank path end to end on one GPU (smoke solve, posted all-reduce, on-chip slab solve): functional, timings meaningless
-timeout 600 python bench.py --gpus 8 --share-gpu --size 4096 --steps 1 --warmup 0 --liters 40 --no-cpu-baseline > $out/bench_8ranks_shared_gpu_4096.json 2> $out/bench_8ranks.err
+timeout 600 python bench.py --full --gpus 8 --share-gpu --size 4096 --steps 1 --warmup 0 --liters 40 --no-cpu-baseline > $out/bench_8ranks_shared_gpu_4096.json 2> $out/bench_8ranks.err
 # one-GPU slab plumbing table and the long-horizon tables
 timeout 600 python tools/slab_overhead.py > $out/slab_overhead.txt 2>&1
 timeout 600 python tools/horizon_parity.py --out $out/horizon_parity > $out/horizon_parity.log 2>&1

@@ -20,7 +20,7 @@ cp $out/kt_onchip/*kernel_stats.csv $out/onchip_kernel_stats.csv 2>/dev/null
 # The counters are folded into profiles/<tag>_traffic.json on the box first, so that the bench line below carries the traffic measured for this very tree
 # (bench.py accepts a traffic file only if its kernel-source hash matches).
 python tools/summarize_profile.py $out profiles/$tag > $out/summarize.log 2>&1
-timeout 600 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 timeout 600 python tools/bench_configs.py > $out/configs.json 2> $out/configs.err
 smi
 cp $out/rocm_smi.txt profiles/${tag}_rocm_smi.txt 2>/dev/null

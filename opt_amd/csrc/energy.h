@@ -11,6 +11,8 @@
 
 namespace optamd {
 
+struct OnchipGuard;      // onchip_sync.h
+
 // Row-slab description of an image problem tiled over several GPUs (OptAmd_PlanSetSlab).  Local arrays
 // hold rows [0,H); rows [yBegin,yEnd) are owned (computed here); local row y is global row gy0+y, which
 // exists iff 0 <= gy0+y < Hg.  Single GPU: yBegin=0, yEnd=H, gy0=0, Hg=H.
@@ -177,29 +179,22 @@ struct EnergyOps {
     int (*onChipPlan)(void*, int, int, int, long, OptAmd_OnChipLinks*) = nullptr;
     void* onChipCtx = nullptr;
     // Row slabs, behind a pcgSolveOnChip launch (which then applies nothing itself): onChipVerdict leaves this rank's verdict (0 fine / 1 failed) in a device scalar, the
-    // solver all-reduces it, onChipApply applies X += delta iff the sum is 0 -- every rank keeps its update or none does -- and tells the host (onChipFailed).
+    // solver all-reduces it, onChipApply applies X += delta iff the sum is 0 -- every rank keeps its update or none does -- and tells the host (OnchipGuard::failedNow).
     virtual void onChipVerdict(double* /*out*/, bool /*refused*/, LaunchCtx&) {}
     virtual void onChipApply(const T* /*delta*/, const double* /*verdict*/, bool /*refused*/, LaunchCtx&) {}
     // OptAmd_PlanDescribe: which linear-solve path the kernel set would take for the plan as it stands (dims, slab), as "key=value; ..." -- bench.py --dry prints it per
     // rank so that a multi-GPU run can be read before it is started.
     virtual std::string describe(int /*lIterations*/, bool /*lm*/) { return "path=launch-per-iteration"; }
-    // After the stream has drained: did a wait inside the last on-chip solve time out (another tenant on the GPU kept its workgroups from being co-resident)?
-    // Then the unknowns were left untouched, the kernel set has switched the path off for this plan, and the caller redoes the linear solve.
-    virtual bool onChipFailed() { return false; }
-    // the same question without consuming the answer (the solver prints an on-chip LM solve's "breaking at iteration" message only for a launch that did not fail)
-    virtual bool onChipFailedPeek() { return false; }
-    // The solver's back-off after such a failure is over: clear the failure state (device word, pinned word, the path's own off switch) so that the next
-    // pcgSolveOnChip launches again.  Stream-ordered.
-    virtual void onChipRearm(LaunchCtx&) {}
+    // The time-out protocol of pcgSolveOnChip (onchip_sync.h OnchipGuard): after the stream has drained the solver asks it whether a wait inside the last on-chip solve timed out
+    // (another tenant on the GPU kept the workgroups from being co-resident) -- then the unknowns were left untouched, the path is off for this plan and the solver redoes
+    // the linear solve -- and switches the path back on after its back-off.  nullptr: the kernel set has no on-chip solve.
+    virtual OnchipGuard* onChipGuard() { return nullptr; }
     // Opt_ProblemSolve may enqueue several Gauss-Newton steps before it reads anything back (PcgSolver: deferred steps).  A kernel set that supports it gives every such
-    // step's guarded update a word of its own (slot >= 0; -1: none), so that the host can tell afterwards WHICH step's on-chip solve gave up -- from that step on nothing was
-    // applied (the failure flag is sticky until onChipRearm) and the solver goes back to it.
+    // step's guarded update a word of its own (OnchipGuard::setStepSlot), so that the host can tell afterwards WHICH step's on-chip solve gave up -- from that step on nothing
+    // was applied (the failure flag is sticky until OnchipGuard::rearm) and the solver goes back to it.
+    virtual bool supportsDeferredSteps() const { return false; }
     // pcgIteration takes delta from its arguments at every launch and keeps no pointer to it: the solver may move the vector between two launches (PcgSolver::deltaTrial)
     virtual bool deltaMovable() const { return false; }
-    virtual bool supportsDeferredSteps() const { return false; }
-    virtual void onChipStepSlot(int /*slot*/) {}
-    virtual bool onChipStepFailed(int /*slot*/) { return false; }
-    virtual void onChipClearStepSlots() {}
     // Slab mode, before the loop: will pcgIteration accept the launches?  (The solver refreshes the ghost rows of r_0, p_0 and M for that loop only: the
     // three-kernel loop relies on r being 0 on ghost rows -- its flat sums run over them.)
     virtual bool slabIterationAvailable() const { return true; }

@@ -233,16 +233,14 @@ struct OpticalFlowOps : StencilOps<T, OpticalFlowE<T>> {
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
         if (!useMarch || traceDev || this->slab.active) return false;
         int sx, ty, G;
-        if (!oc.enabled || oc.failed || (lm && (!lm->CtC || lm->resetPeriod < L)) ||
+        if (!oc.guard.usable() || (lm && (!lm->CtC || lm->resetPeriod < L)) ||
             !(lm ? oc.template select<FlowMarchOp<T>, true>(this->e.W, this->e.H, this->cus, sx, ty, G) : oc.template select<FlowMarchOp<T>, false>(this->e.W, this->e.H, this->cus, sx, ty, G))) return false;      // (before the coefficient pass is spent)
         const long n = (long)this->e.W * this->e.H;
         if (!coef) HIP_CHECK(hipMalloc((void**)&coef, (size_t)(2 * n) * sizeof(T)));
         { ScopedKernel k(ctx, "operatorCoefficients"); flow_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e, coef); }
         return oc.solve(FlowMarchOp<T>{this->e.w_fit, this->e.w_reg}, this->e.W, this->e.H, nullptr, coef, r0, p0, delta, const_cast<T*>(this->e.X[0]), L, this->cus, ctx, lm);
     }
-    bool onChipFailed() override { return oc.failedNow(); }
-    bool onChipFailedPeek() override { return oc.failedPeek(); }
-    void onChipRearm(LaunchCtx& ctx) override { oc.rearm(ctx); }
+    OnchipGuard* onChipGuard() override { return &oc.guard; }
     std::string describe(int L, bool lmv) override { return oc.template describe<FlowMarchOp<T>>(this->e.W, this->e.H, this->cus, useMarch ? L : 0, lmv, "march_pcgIter"); }
 };
 template <class T> EnergyOps<T>* makeFlow(const unsigned* dims) { return new OpticalFlowOps<T>(dims); }
@@ -299,7 +297,7 @@ struct IntrinsicOps : StencilOps<T, IntrinsicE<T>> {
         if (!useMarch || traceDev || this->slab.active) return false;
         using Op = IntrinsicMarchOp<T>;
         int sx, ty, G;
-        if (!oc.enabled || oc.failed || (lm && (!lm->CtC || lm->resetPeriod < L)) ||
+        if (!oc.guard.usable() || (lm && (!lm->CtC || lm->resetPeriod < L)) ||
             !(lm ? oc.template select<Op, true>(this->e.W, this->e.H, this->cus, sx, ty, G) : oc.template select<Op, false>(this->e.W, this->e.H, this->cus, sx, ty, G))) return false;
         const long n = (long)this->e.W * this->e.H;
         if (!coef) HIP_CHECK(hipMalloc((void**)&coef, (size_t)(4 * n) * sizeof(T)));
@@ -309,19 +307,17 @@ struct IntrinsicOps : StencilOps<T, IntrinsicE<T>> {
     }
     bool onChipAppliedUpdate() const override { return false; }
     bool onChipGuardedUpdate(const T* delta, LaunchCtx& ctx) override {      // X += delta per unknown image, unless the launch raised its failure word
-        if (!oc.bad || !oc.launched) return false;
+        if (!oc.guard.bad || !oc.guard.launched) return false;
         ScopedKernel k(ctx, "PCGLinearUpdate");
         for (size_t i = 0; i < this->unknowns.size(); ++i) {
             const auto& u = this->unknowns[i];
             const long cnt = u.elems * u.channels;
             const int grid = (int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, 4096));
-            march_applyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(this->unknownPtr((int)i), delta + u.offset, cnt, oc.bad, oc.hostErr);
+            march_applyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(this->unknownPtr((int)i), delta + u.offset, cnt, oc.guard.bad, oc.guard.hostErr);
         }
         return true;
     }
-    bool onChipFailed() override { return oc.failedNow(); }
-    bool onChipFailedPeek() override { return oc.failedPeek(); }
-    void onChipRearm(LaunchCtx& ctx) override { oc.rearm(ctx); }
+    OnchipGuard* onChipGuard() override { return &oc.guard; }
     std::string describe(int L, bool lmv) override { return oc.template describe<IntrinsicMarchOp<T>>(this->e.W, this->e.H, this->cus, useMarch ? L : 0, lmv, "march_pcgIter"); }
 };
 template <class T> EnergyOps<T>* makeIntrinsic(const unsigned* dims) { return new IntrinsicOps<T>(dims); }

@@ -49,19 +49,12 @@ struct ImageWarpingOps : EnergyOps<T> {
         if (const char* e = getenv("OPT_AMD_SLAB_PERIOD")) maxExchangePeriod = std::max(1, atoi(e));
         if (const char* e = getenv("OPT_AMD_ITER_ROWS")) forceRows = std::max(0, atoi(e));
         if (const char* e = getenv("OPT_AMD_ITER_MAXWG")) maxWorkgroups = std::max(1, atoi(e));
-        if (const char* e = getenv("OPT_AMD_ONCHIP")) ocEnabled = atoi(e) != 0;
-        if (const char* e = getenv("OPT_AMD_ONCHIP_ROWS")) ocForceRows = std::max(0, atoi(e));
         if (const char* e = getenv("OPT_AMD_ONCHIP_FLAT")) ocFlatMax = std::max(0, atoi(e));
-        if (const char* e = getenv("OPT_AMD_ONCHIP_FAIL_AT")) ocFailAt = atoi(e);      // test hook: see OnchipArgs::failAt
-        if (const char* e = getenv("OPT_AMD_ONCHIP_FAIL_LAUNCH")) ocFailLaunch = atoi(e);      // ... in the n-th on-chip launch of the plan only (default: in every one)
-        if (const char* e = getenv("OPT_AMD_ONCHIP_TIMEOUT_MS")) ocTimeoutTicks = std::max(1, atoi(e)) * 100000LL;
         HIP_CHECK(hipMalloc((void**)&dNotLattice, sizeof(int)));
         HIP_CHECK(hipHostMalloc((void**)&hNotLattice, 64)); *hNotLattice = 0;
         HIP_CHECK(hipEventCreateWithFlags(&bindEvent, hipEventDisableTiming));
     }
     ~ImageWarpingOps() override {
-        if (ocS.slots) { (void)hipFree(ocS.slots); (void)hipFree(ocS.groupSlots); (void)hipFree(ocS.inbox); }
-        if (ocS.bad) { (void)hipFree(ocS.bad); (void)hipHostFree(ocS.hostErr); }
         (void)hipHostFree(hNotLattice); (void)hipEventDestroy(bindEvent);
         for (T* b : ring) if (b) (void)hipFree(b);
         (void)hipFree(A.flags); (void)hipFree(A.cs); if (alphaSlots) (void)hipFree(alphaSlots); (void)hipFree(dNotLattice);
@@ -450,13 +443,13 @@ struct ImageWarpingOps : EnergyOps<T> {
     long rowScalars(int img) const override { return (long)A.W * (img == 0 ? 2 : 1); }
 
     // ---- the whole linear solve on chip (iw_onchip.h): unit lattice, Gauss-Newton (also on row slabs) or Levenberg-Marquardt, tiles <= CUs ------------------------------------------
-    // OPT_AMD_ONCHIP=0 switches it off (the one A/B switch of the path); OPT_AMD_ONCHIP_ROWS=r forces the variant with r rows per lane (tests run every
-    // variant on small images); OPT_AMD_ONCHIP_FLAT=n: grids of up to n workgroups sum flat instead of through the two-level tree (same bits either way).
+    // OPT_AMD_ONCHIP* (onchip_sync.h OnchipGuard); OPT_AMD_ONCHIP_FLAT=n: grids of up to n workgroups sum flat instead of through the two-level tree (same bits either way).
     struct OcVariant { int rows; bool apLds, deltaGlb; const void* fn; size_t lds; int occ; };
     std::vector<OcVariant> ocVariants, ocVariantsLM;
-    bool ocEnabled = true, ocFailed = false, ocLaunched = false;
-    int ocForceRows = 0, ocFlatMax = 256, ocFailAt = -1, ocFailLaunch = -1, ocLaunchCount = 0; long long* ocProf = nullptr; long long ocTimeoutTicks = 0;      // 0: onchip_sync.h ocTimeouts() decides; OPT_AMD_ONCHIP_TIMEOUT_MS overrides
-    OnchipSync ocS{}; unsigned ocSeq = 1; size_t ocInboxBytes = 0, ocSlotBytes = 0, ocGroupBytes = 0;
+    OnchipGuard guard;
+    OnchipGuard* onChipGuard() override { return &guard; }
+    int ocFlatMax = 256; long long* ocProf = nullptr;
+    OnchipSync ocS{};      // the tagged buffers (bad, hostErr: the guard's, filled in at the launch)
     void ocInit() {
         if (!ocVariants.empty()) return;
         if constexpr (sizeof(T) == 4) {
@@ -486,7 +479,7 @@ struct ImageWarpingOps : EnergyOps<T> {
         tX = divUp(A.W, kOcTileW);
         const int rowsOwned = A.yEnd - A.yBegin;
         for (const auto& v : lmv ? ocVariantsLM : ocVariants) {
-            if (ocForceRows && v.rows != ocForceRows) continue;
+            if (guard.forceRows && v.rows != guard.forceRows) continue;
             const int th = kOcWavesY * v.rows;
             if (this->slab.active && rowsOwned % th != 0) continue;
             tY = divUp(rowsOwned, th);
@@ -496,7 +489,7 @@ struct ImageWarpingOps : EnergyOps<T> {
     }
     bool slabOnChipAvailable(int L) override {      // (row slabs: the lattice verdict of this bind is already known, bind() read it back)
         int tX, tY;
-        if (!(ocEnabled && !ocFailed && L > 0 && this->slab.active && this->slab.ghost >= 2 && this->onChipPlan && lattice &&
+        if (!(guard.usable() && L > 0 && this->slab.active && this->slab.ghost >= 2 && this->onChipPlan && lattice &&
               (unsigned long long)A.W * A.H * 3ull * sizeof(T) < (1ull << 32) && ocSelect(tX, tY) != nullptr)) return false;
         // ... and the communicator could plan it (count = 0: a dry query -- its sticky error state and the capacity of its edge boxes -- so that a "no" is part of the vote)
         return this->onChipPlan(this->onChipCtx, 4, 0, tX, 3L * kOcTileW * (long)(sizeof(T) / 4), nullptr) != 0;
@@ -504,7 +497,7 @@ struct ImageWarpingOps : EnergyOps<T> {
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lmArgs, LaunchCtx& ctx) override {
         const bool slabMode = this->slab.active;
         if (lmArgs && (slabMode || traceDev || lmArgs->resetPeriod < 1)) return false;      // the LM variants are single-GPU
-        if (!ocEnabled || ocFailed || L <= 0 || (unsigned long long)A.W * A.H * 3ull * sizeof(T) >= (1ull << 32)) return false;
+        if (!guard.usable() || L <= 0 || (unsigned long long)A.W * A.H * 3ull * sizeof(T) >= (1ull << 32)) return false;
         if (slabMode && (traceDev || !slabOnChipAvailable(L))) return false;
         resolveLattice();
         if (initPending && initHint && !lattice) { launchJtf(false, ctx); initHint = false; }      // PCGInit1 ran on the previous bind's verdict (see beginLoop)
@@ -514,24 +507,17 @@ struct ImageWarpingOps : EnergyOps<T> {
         if (!V) return false;
         const int G = tX * tY;
         if (lmArgs && G > ocFlatMax) return false;      // (the LM variants sum flat)
-        if (!ocS.slots) {      // sized for this plan's image once (the dimensions of a plan are fixed); zero = no tag
+        if (!ocS.slots) {      // sized for this plan's image once (the dimensions of a plan are fixed); cleared by the first guard.tags()
             const int maxRows = ocVariants.front().rows;
             const int gMax = std::min(kOcMaxTiles, tX * divUp(A.yEnd - A.yBegin, kOcWavesY * maxRows));
             ocS.stride = 3L * kOcTileW * (long)(sizeof(T) / 4);
-            ocSlotBytes = sizeof(oc_u64) * 2 * (size_t)gMax * 2 * kOcSumsMax; ocGroupBytes = sizeof(oc_u64) * 2 * (size_t)divUp(gMax, kOcGroup) * 8;
-            ocInboxBytes = sizeof(oc_u64) * 2 * (size_t)gMax * 4 * (size_t)ocS.stride;
-            HIP_CHECK(hipMalloc((void**)&ocS.slots, ocSlotBytes)); HIP_CHECK(hipMalloc((void**)&ocS.groupSlots, ocGroupBytes)); HIP_CHECK(hipMalloc((void**)&ocS.inbox, ocInboxBytes));
-            if (!ocS.bad) { HIP_CHECK(hipMalloc((void**)&ocS.bad, sizeof(int))); HIP_CHECK(hipHostMalloc((void**)&ocS.hostErr, 64)); for (int w_ = 0; w_ < 16; ++w_) ocS.hostErr[w_] = 0; HIP_CHECK(hipMemsetAsync(ocS.bad, 0, sizeof(int), ctx.stream)); }
-            ocSeq = 0xE0000001u;      // forces the clearing below
+            ocS.slots = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)gMax * 2 * kOcSumsMax);
+            ocS.groupSlots = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)divUp(gMax, kOcGroup) * 8);
+            ocS.inbox = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)gMax * 4 * (size_t)ocS.stride);
+            guard.allocWords(ctx.stream);
 #if OC_PROFILE
             if (getenv("OPT_AMD_ONCHIP_PROFILE")) { HIP_CHECK(hipMalloc((void**)&ocProf, sizeof(long long) * kOcWaves * 16 * kOcMaxTiles)); }
 #endif
-        }
-        const unsigned nTags = lmArgs ? 2u * (unsigned)L : (unsigned)L;      // (an LM iteration that ends with the split residual reset has two phases)
-        if (ocSeq > 0xE0000000u || ocSeq + nTags > 0xE0000000u) {      // tags never repeat: start over on cleared buffers long before the counter wraps
-            HIP_CHECK(hipMemsetAsync(ocS.slots, 0, ocSlotBytes, ctx.stream)); HIP_CHECK(hipMemsetAsync(ocS.groupSlots, 0, ocGroupBytes, ctx.stream));
-            HIP_CHECK(hipMemsetAsync(ocS.inbox, 0, ocInboxBytes, ctx.stream));
-            ocSeq = 2;
         }
         OcLinks links{};
         if (slabMode) {      // (every rank makes this call: the solver has made the decision to run on chip collective)
@@ -542,18 +528,18 @@ struct ImageWarpingOps : EnergyOps<T> {
             links.seq0 = Lk.seq0; links.edgeSendUp = Lk.edgeSendUp; links.edgeSendDown = Lk.edgeSendDown; links.edgeRecvUp = Lk.edgeRecvUp; links.edgeRecvDown = Lk.edgeRecvDown;
             links.edgeParityStride = Lk.edgeParityStride;
         }
-        const OcTimeouts tmo = ocTimeouts(ocTimeoutTicks, L, slabMode);
-        OnchipArgs<T> K{A.W, A.H, tX, tY, G, A.yBegin, A.yEnd, links, r0, p0, A.Angle, A.flags, delta, A.w_fit, A.w_reg, L, ocSeq, G <= ocFlatMax ? 1 : 0, ocS, lmArgs ? lmArgs->breakInfo : traceDev,
-                        tmo.later, tmo.first, ocProf, (ocFailLaunch < 0 || ocLaunchCount == ocFailLaunch) ? ocFailAt : -1, T(0), T(0), T(0), T(0), 1};
-        ++ocLaunchCount;
+        const unsigned tag0 = guard.tags(lmArgs ? 2u * (unsigned)L : (unsigned)L, ctx.stream);      // (an LM iteration that ends with the split residual reset has two phases)
+        const OcTimeouts tmo = guard.timeouts(L, slabMode);
+        OnchipArgs<T> K{A.W, A.H, tX, tY, G, A.yBegin, A.yEnd, links, r0, p0, A.Angle, A.flags, delta, A.w_fit, A.w_reg, L, tag0, G <= ocFlatMax ? 1 : 0, ocS, lmArgs ? lmArgs->breakInfo : traceDev,
+                        tmo.later, tmo.first, ocProf, guard.failAtThisLaunch(), T(0), T(0), T(0), T(0), 1};
+        K.S.bad = guard.bad; K.S.hostErr = guard.hostErr;
         if (lmArgs) { K.lmRadius = lmArgs->radius; K.lmMin = lmArgs->minLm; K.lmMax = lmArgs->maxLm; K.qTolerance = lmArgs->qTolerance; K.resetPeriod = lmArgs->resetPeriod; }
-        ocSeq += nTags;
         {
             ScopedKernel k(ctx, "PCGSolveOnChip");
             void* kargs[] = {(void*)&K};
             HIP_CHECK(hipLaunchKernel(V->fn, dim3(G), dim3(kOcBlock), kargs, V->lds, ctx.stream));
         }
-        if (lmArgs) { iw_relayBad<<<1, kWave, 0, ctx.stream>>>(ocS.bad, ocS.hostErr); ocLaunched = true; }      // (the solver applies the update itself)
+        if (lmArgs) { iw_relayBad<<<1, kWave, 0, ctx.stream>>>(guard.bad, guard.hostErr); guard.launched = true; }      // (the solver applies the update itself)
         else if (!slabMode) onChipApply(delta, nullptr, false, ctx);      // (row slabs: the solver all-reduces the ranks' verdicts first, then calls onChipApply)
 #if OC_PROFILE
         if (ocProf) {      // development builds: where an iteration's time goes, per wave of a workgroup, mean over the workgroups
@@ -582,15 +568,14 @@ struct ImageWarpingOps : EnergyOps<T> {
     // PCGLinearUpdate behind the on-chip Gauss-Newton solve.  verdict (row slabs): device scalar, the number of ranks whose kernel failed -- all ranks apply or none.
     // refused: this rank launched no kernel at all (its peers will time out): its contribution to the verdict is "failed".
     void onChipVerdict(double* out, bool refused, LaunchCtx& ctx) override {
-        if (!ocS.bad) { HIP_CHECK(hipMalloc((void**)&ocS.bad, sizeof(int))); HIP_CHECK(hipHostMalloc((void**)&ocS.hostErr, 64)); for (int w_ = 0; w_ < 16; ++w_) ocS.hostErr[w_] = 0; HIP_CHECK(hipMemsetAsync(ocS.bad, 0, sizeof(int), ctx.stream)); }
-        iw_badToScalar<<<1, kWave, 0, ctx.stream>>>(ocS.bad, refused ? 1 : 0, out);
+        guard.allocWords(ctx.stream);
+        iw_badToScalar<<<1, kWave, 0, ctx.stream>>>(guard.bad, refused ? 1 : 0, out);
     }
     void onChipApply(const T* delta, const double* verdict, bool /*refused*/, LaunchCtx& ctx) override {
         ScopedKernel k(ctx, "PCGLinearUpdate");
         const long N = (long)A.W * A.H;
-        iw_applyDelta<T><<<flatGrid(N), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.Offset), const_cast<T*>(A.Angle), delta, N, ocS.bad, verdict, ocS.hostErr,
-                                                                 ocStepSlot >= 0 ? ocS.hostErr + 1 + ocStepSlot : nullptr);
-        ocLaunched = true;
+        iw_applyDelta<T><<<flatGrid(N), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.Offset), const_cast<T*>(A.Angle), delta, N, guard.bad, verdict, guard.hostErr, guard.stepWord());
+        guard.launched = true;
     }
     std::string describe(int L, bool lmv) override {      // ("key=value; ..." -- no ';' inside a value)
         const Slab& sl = this->slab;
@@ -598,7 +583,7 @@ struct ImageWarpingOps : EnergyOps<T> {
         char buf[900];
         if (sl.active) { A.yBegin = sl.yBegin; A.yEnd = sl.yEnd; } else { A.yBegin = 0; A.yEnd = A.H; }      // (what bind() will set: ocSelect reads them)
         int tX = 0, tY = 0;
-        const bool eligible = ocEnabled && !ocFailed && L > 0 && !(lmv && sl.active);
+        const bool eligible = guard.usable() && L > 0 && !(lmv && sl.active);
         const OcVariant* V = eligible ? ocSelect(tX, tY, lmv) : nullptr;
         // the same question without the workgroup cap of ranks that SHARE a GPU (OPT_AMD_ITER_MAXWG): what one GPU per rank would answer
         int uX = 0, uY = 0; const OcVariant* U = nullptr;
@@ -612,7 +597,7 @@ struct ImageWarpingOps : EnergyOps<T> {
                      sl.active ? " and every rank and the communicator agree" : "", V->rows, tX, tY, cus, V->lds, rowsOwned, sl.active ? sl.ghost : 0, cap.c_str(),
                      sl.active ? "edge rows of A p as tagged words (2 x W x 3 scalars x 8 B per neighbour) + one rank hop of 4 doubles, inside the persistent launch" : "none");
         else {
-            const std::string why = !ocEnabled ? "switched off" : ocFailed ? "a wait timed out earlier" : (lmv && sl.active) ? "the LM variants are single-GPU" : !ghostOk ? "needs >= 2 ghost rows" :
+            const std::string why = guard.whyOff() ? guard.whyOff() : (lmv && sl.active) ? "the LM variants are single-GPU" : !ghostOk ? "needs >= 2 ghost rows" :
                                     U ? "the workgroup cap -- without it: on-chip, " + std::to_string(U->rows) + " rows per lane, " + std::to_string(uX) + "x" + std::to_string(uY) + " tiles" :
                                     "the tiles do not fit one per CU (or the slab is no whole number of tiles)";
             const std::string cross = sl.active ? "one all-reduce of 4 doubles, and every " + std::to_string(std::max(1, sl.ghost - 1)) + " iterations " + std::to_string(2L * sl.ghost * rowBytes) +
@@ -622,26 +607,8 @@ struct ImageWarpingOps : EnergyOps<T> {
         }
         return buf;
     }
-    bool onChipFailed() override {
-        if (!ocLaunched) return false;
-        ocLaunched = false;
-        if (__atomic_load_n(ocS.hostErr, __ATOMIC_ACQUIRE) == 0) return false;
-        ocFailed = true;
-        return true;
-    }
-    bool onChipFailedPeek() override { return ocLaunched && ocS.hostErr && __atomic_load_n(ocS.hostErr, __ATOMIC_ACQUIRE) != 0; }
-    int ocStepSlot = -1;      // (hostErr is 16 ints: word 0 "some launch failed", words 1 .. 15 one per deferred step)
     bool supportsDeferredSteps() const override { return !this->slab.active; }
     bool deltaMovable() const override { return !this->slab.active; }
-    void onChipStepSlot(int slot) override { ocStepSlot = (slot >= 0 && slot < 15) ? slot : -1; }
-    bool onChipStepFailed(int slot) override { return ocS.hostErr && slot >= 0 && slot < 15 && __atomic_load_n(ocS.hostErr + 1 + slot, __ATOMIC_ACQUIRE) != 0; }
-    void onChipClearStepSlots() override { if (ocS.hostErr) for (int i = 1; i < 16; ++i) __atomic_store_n(ocS.hostErr + i, 0, __ATOMIC_RELEASE); }
-    void onChipRearm(LaunchCtx& ctx) override {
-        if (!ocS.bad) return;
-        onChipClearStepSlots();
-        ocFailed = false; __atomic_store_n(ocS.hostErr, 0, __ATOMIC_RELEASE);
-        HIP_CHECK(hipMemsetAsync(ocS.bad, 0, sizeof(int), ctx.stream));
-    }
 };
 
 template <class T> EnergyOps<T>* makeIW(const unsigned* dims) { return new ImageWarpingOps<T>(dims); }

@@ -636,14 +636,9 @@ struct SfsOps : EnergyOps<T> {
         if (const char* e = getenv("OPT_AMD_SFS_ONEKERNEL")) oneKernel = atoi(e) != 0;
         gridOverride = devSwitch("OPT_AMD_SFS_GRID", gridOverride);
         if (const char* e = getenv("OPT_AMD_SFS_MARCH_GRID")) marchGridOverride = atoi(e);
-        if (const char* e = getenv("OPT_AMD_ONCHIP")) soEnabled = atoi(e) != 0;
-        if (const char* e = getenv("OPT_AMD_ONCHIP_ROWS")) soForceRows = std::max(0, atoi(e));
-        if (const char* e = getenv("OPT_AMD_ONCHIP_WAVES")) soForceWaves = std::max(0, atoi(e));
-        if (const char* e = getenv("OPT_AMD_ONCHIP_FAIL_AT")) soFailAt = atoi(e);      // test hook: see SfsOcArgs::failAt
-        if (const char* e = getenv("OPT_AMD_ONCHIP_TIMEOUT_MS")) soTimeoutTicks = std::max(1, atoi(e)) * 100000LL;
         soReserve();
     }
-    ~SfsOps() override { for (void* p : owned) (void)hipFree(p); if (soHostErr) (void)hipHostFree(soHostErr); }
+    ~SfsOps() override { for (void* p : owned) (void)hipFree(p); }
     int grid() const { return (int)std::max<long>(1, std::min<long>(((long)A.W * A.H + kBlock - 1) / kBlock, std::min<long>(kMaxPartials, (long)cus * 8))); }
     void bind(void** p, LaunchCtx&) override {
         // sqrt(Param(...)) is evaluated in opt_float on the float parameter (shape_from_shading.t:4-6)
@@ -752,13 +747,12 @@ struct SfsOps : EnergyOps<T> {
     }
 
     // ---- the whole linear solve on chip (sfs_onchip.h): Gauss-Newton or Levenberg-Marquardt, one GPU, workgroups <= CUs ---------------------------------------------
-    // OPT_AMD_ONCHIP=0 switches it off (the one A/B switch of the path); OPT_AMD_ONCHIP_ROWS=r / OPT_AMD_ONCHIP_WAVES=w force the variant that owns r rows per wave / has w waves per workgroup (tests run
-    // every variant on small images); OPT_AMD_ONCHIP_FAIL_AT / _TIMEOUT_MS: the time-out path's test hooks.
+    // OPT_AMD_ONCHIP* (onchip_sync.h OnchipGuard): ROWS=r / WAVES=w force the variant that owns r rows per wave / has w waves per workgroup.
     struct SoVariant { int rows, waves; const void* gn; const void* lm; };
-    bool soEnabled = true, soFailed = false, soLaunched = false;
-    int soForceRows = 0, soForceWaves = 0, soFailAt = -1; long long soTimeoutTicks = 0;      // 0: onchip_sync.h ocTimeouts() decides; OPT_AMD_ONCHIP_TIMEOUT_MS overrides
+    OnchipGuard guard;
+    OnchipGuard* onChipGuard() override { return &guard; }
     long long* soProf = nullptr;
-    oc_u64 *soSlots = nullptr, *soBox = nullptr; int *soBad = nullptr, *soHostErr = nullptr; unsigned soSeq = 0; size_t soSlotBytes = 0, soBoxBytes = 0;
+    oc_u64 *soSlots = nullptr, *soBox = nullptr;      // the tagged buffers
     static const std::vector<SoVariant>& soVariants() {
         static const std::vector<SoVariant> v = [] {
             std::vector<SoVariant> o;
@@ -776,8 +770,8 @@ struct SfsOps : EnergyOps<T> {
         stripsX = divUp(A.W, kSoSpan);
         const SoVariant* best = nullptr; int bestCost = 1 << 30;
         for (const auto& v : soVariants()) {
-            if (soForceRows && v.rows != soForceRows) continue;
-            if (soForceWaves && v.waves != soForceWaves) continue;
+            if (guard.forceRows && v.rows != guard.forceRows) continue;
+            if (guard.forceWaves && v.waves != guard.forceWaves) continue;
             const int ty = divUp(A.H, v.rows), g = divUp(stripsX * ty, v.waves);
             if (g > std::min(cus, kSoMaxG)) continue;
             const int cost = (v.waves == 4 ? 100 : 136) * (v.rows + 4);      // (measured: two waves per SIMD march a pair of trips in 1.36 of the time one wave marches one)
@@ -785,41 +779,34 @@ struct SfsOps : EnergyOps<T> {
         }
         return best;
     }
-    // the buffers of the path, sized for the plan's image when the plan is made (so that its first linear solve does not pay for the allocations); zero = no tag
+    // the buffers of the path, sized for the plan's image when the plan is made (so that its first linear solve does not pay for the allocations)
     void soReserve() {
-        if (soSlots || !soEnabled || (unsigned long long)A.W * A.H * sizeof(T) >= (1ull << 30)) return;
+        if (soSlots || !guard.enabled || (unsigned long long)A.W * A.H * sizeof(T) >= (1ull << 30)) return;
         { int sx, ty, g; if (!soSelect(sx, ty, g)) return; }      // (the image does not fit the chip: the path will never be taken)
-        soSlotBytes = sizeof(oc_u64) * 2 * (size_t)kSoMaxG * kSoNW; soBoxBytes = sizeof(oc_u64) * 2 * (size_t)A.W * A.H * (sizeof(T) / 4);
-        HIP_CHECK(hipMalloc((void**)&soSlots, soSlotBytes)); owned.push_back(soSlots);
-        HIP_CHECK(hipMalloc((void**)&soBox, soBoxBytes)); owned.push_back(soBox);
-        HIP_CHECK(hipMalloc((void**)&soBad, sizeof(int))); owned.push_back(soBad);
-        HIP_CHECK(hipHostMalloc((void**)&soHostErr, 64)); *soHostErr = 0;
-        HIP_CHECK(hipMemset(soBad, 0, sizeof(int))); HIP_CHECK(hipMemset(soSlots, 0, soSlotBytes)); HIP_CHECK(hipMemset(soBox, 0, soBoxBytes)); HIP_CHECK(hipStreamSynchronize(nullptr));      // (done before the plan's own stream sees the buffers)
-        soSeq = 2;
+        soSlots = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)kSoMaxG * kSoNW);
+        soBox = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)A.W * A.H * (sizeof(T) / 4));
+        guard.allocWords(nullptr); guard.clearTagged(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr));      // (done before the plan's own stream sees the buffers)
 #if SO_PROFILE
         if (getenv("OPT_AMD_ONCHIP_PROFILE")) { HIP_CHECK(hipMalloc((void**)&soProf, sizeof(long long) * 8 * kSoMaxG)); owned.push_back(soProf); }
 #endif
     }
     bool onChipWithoutPreconditioner() const override { return true; }
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lmArgs, LaunchCtx& ctx) override {
-        if (!soEnabled || soFailed || this->slab.active || traceDev || L <= 0 || (unsigned long long)A.W * A.H * sizeof(T) >= (1ull << 30)) return false;
+        if (!guard.usable() || this->slab.active || traceDev || L <= 0 || (unsigned long long)A.W * A.H * sizeof(T) >= (1ull << 30)) return false;
         if (lmArgs && (!lmArgs->CtC || lmArgs->resetPeriod < L)) return false;      // a split residual reset before the last iteration: the marching loop's business
         int stripsX = 0, tilesY = 0, G = 0;
         const SoVariant* V = soSelect(stripsX, tilesY, G);
         if (!V) return false;
         if (!soSlots) { soReserve(); if (!soSlots) return false; }
-        if (soSeq > 0xE0000000u || soSeq + (unsigned)L > 0xE0000000u) {      // tags never repeat: start over on cleared buffers long before the counter wraps
-            HIP_CHECK(hipMemsetAsync(soSlots, 0, soSlotBytes, ctx.stream)); HIP_CHECK(hipMemsetAsync(soBox, 0, soBoxBytes, ctx.stream));
-            soSeq = 2;
-        }
-        const OcTimeouts tmo = ocTimeouts(soTimeoutTicks, L, false);
-        SfsOcArgs<T> K{A, r0, p0, lmArgs ? lmArgs->CtC : nullptr, delta, stripsX, tilesY, G, L, soSeq, soSlots, soBox, soBad, tmo.later, soFailAt, tmo.first, lmArgs ? lmArgs->qTolerance : T(0), lmArgs ? soHostErr : nullptr, soProf, lmArgs ? lmArgs->breakInfo : nullptr};
-        soSeq += (unsigned)L;
+        const unsigned tag0 = guard.tags((unsigned)L, ctx.stream);
+        const OcTimeouts tmo = guard.timeouts(L, false);
+        SfsOcArgs<T> K{A, r0, p0, lmArgs ? lmArgs->CtC : nullptr, delta, stripsX, tilesY, G, L, tag0, soSlots, soBox, guard.bad, tmo.later, guard.failAtThisLaunch(), tmo.first, lmArgs ? lmArgs->qTolerance : T(0),
+                       lmArgs ? guard.hostErr : nullptr, soProf, lmArgs ? lmArgs->breakInfo : nullptr};
         {
             ScopedKernel k(ctx, "PCGSolveOnChip");
             void* kargs[] = {(void*)&K};
             if (hipLaunchKernel(lmArgs ? V->lm : V->gn, dim3(G), dim3(V->waves * kWave), kargs, 0, ctx.stream) != hipSuccess) {      // (a device that cannot hold the variant's LDS: not offered again)
-                (void)hipGetLastError(); soEnabled = false; soSeq -= (unsigned)L;
+                (void)hipGetLastError(); guard.enabled = false;
                 fprintf(stderr, "Opt(amd): the on-chip shape_from_shading kernel (%d rows, %d waves) could not be launched; the plan stays on the marching kernels\n", V->rows, V->waves);
                 return false;
             }
@@ -843,32 +830,19 @@ struct SfsOps : EnergyOps<T> {
         if (!lmArgs) {      // (LM: the solver applies the update itself; a workgroup that gave up has told the host on its way out)
             ScopedKernel k(ctx, "PCGLinearUpdate");
             const long N = (long)A.W * A.H;
-            sfs_applyDelta<T><<<grid(), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.X), delta, N, soBad, soHostErr);
+            sfs_applyDelta<T><<<grid(), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.X), delta, N, guard.bad, guard.hostErr);
         }
-        soLaunched = true;
+        guard.launched = true;
         return true;
-    }
-    bool onChipFailed() override {
-        if (!soLaunched) return false;
-        soLaunched = false;
-        if (__atomic_load_n(soHostErr, __ATOMIC_ACQUIRE) == 0) return false;
-        soFailed = true;
-        return true;
-    }
-    bool onChipFailedPeek() override { return soLaunched && soHostErr && __atomic_load_n(soHostErr, __ATOMIC_ACQUIRE) != 0; }
-    void onChipRearm(LaunchCtx& ctx) override {
-        if (!soBad) return;
-        soFailed = false; __atomic_store_n(soHostErr, 0, __ATOMIC_RELEASE);
-        HIP_CHECK(hipMemsetAsync(soBad, 0, sizeof(int), ctx.stream));
     }
     std::string describe(int L, bool lmv) override {      // ("key=value; ..." -- no ';' inside a value)
         int stripsX = 0, tilesY = 0, G = 0;
-        const SoVariant* V = (soEnabled && !soFailed && !this->slab.active && L > 0) ? soSelect(stripsX, tilesY, G) : nullptr;
+        const SoVariant* V = (guard.usable() && !this->slab.active && L > 0) ? soSelect(stripsX, tilesY, G) : nullptr;
         char buf[600];
         if (V) snprintf(buf, sizeof buf, "path=on-chip (sfs_onchipPcg%s%s); onchip_rows_per_wave=%d; waves_per_workgroup=%d; wave_tiles=%dx%d of 60 x %d pixels; workgroups=%d of %d CUs; fallback=one launch per PCG iteration (sfs_pcgMarch)",
                         lmv ? ", LM" : "", lmv ? " while lIterations <= residual_reset_period" : "", V->rows, V->waves, stripsX, tilesY, V->rows, G, cus);
         else snprintf(buf, sizeof buf, "path=one launch per PCG iteration (sfs_pcgMarch%s); why_not_on_chip=%s", lmv ? ", LM" : "",
-                      !soEnabled ? "switched off" : soFailed ? "a wait timed out earlier" : this->slab.active ? "row slabs" : "the wave tiles do not fit the CUs");
+                      guard.whyOff() ? guard.whyOff() : this->slab.active ? "row slabs" : "the wave tiles do not fit the CUs");
         return buf;
     }
 };

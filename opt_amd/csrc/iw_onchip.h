@@ -793,7 +793,7 @@ __global__ __launch_bounds__(kBlock) void iw_applyDelta(T* __restrict__ XO, T* _
     if (fail) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             __hip_atomic_store(hostErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (stepErr) __hip_atomic_store(stepErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (EnergyOps::onChipStepSlot: which of several enqueued steps this was)
+            if (stepErr) __hip_atomic_store(stepErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (OnchipGuard::setStepSlot: which of several enqueued steps this was)
         }
         return;
     }

@@ -6,11 +6,9 @@
 // over the life of a buffer.  Every wait is bounded by the device's 100 MHz wall clock and gives up as soon as another waiter has (the `bad` word).
 #pragma once
 #include "common.h"
+#include <utility>
 
 namespace optamd {
-namespace {
-
-typedef unsigned long long oc_u64;
 
 // Bounds of the waits inside a persistent kernel, in ticks of the device's 100 MHz wall clock.  `first`: the waits of the first phase -- every workgroup posts its words
 // before it waits, so passing them proves the whole grid resident; a grid that is NOT co-resident (a foreign tenant holds CUs, another plan's persistent kernel) gives up
@@ -25,6 +23,82 @@ inline OcTimeouts ocTimeouts(long long overrideTicks, int lIterations, bool wait
     if (overrideTicks > 0) { t.later = overrideTicks; t.first = std::min(t.first, overrideTicks); }
     return t;
 }
+
+// Host side of a time-out, one per kernel set with a persistent kernel (EnergyOps::onChipGuard).  A wait that gives up raises the device word `bad`; the launch's update
+// kernel (or the kernel itself, where the solver applies the update) relays it to pinned host word 0 and leaves the unknowns untouched; after the stream has drained
+// the solver asks failedNow(), redoes the linear solve on the streaming kernels and calls rearm() once its back-off is over.
+// Switches (read once per plan): OPT_AMD_ONCHIP=0 switches the path off (the one A/B switch); OPT_AMD_ONCHIP_ROWS / _WAVES force a variant (tests run every variant on
+// small images); the test hooks of the time-out path: OPT_AMD_ONCHIP_FAIL_AT=i (workgroup 0 raises `bad` in iteration i as a timed-out wait would), in the n-th on-chip
+// launch of the plan only with OPT_AMD_ONCHIP_FAIL_LAUNCH=n, and OPT_AMD_ONCHIP_TIMEOUT_MS (overrides the bounds above).
+struct OnchipGuard {
+    bool enabled = true, failed = false, launched = false;      // failed: a wait timed out, the path is off until rearm(); launched: a launch reports to hostErr[0]
+    int forceRows = 0, forceWaves = 0, failAt = -1, failLaunch = -1, launches = 0, stepSlot = -1;
+    long long timeoutTicks = 0;      // 0: ocTimeouts() decides
+    int* bad = nullptr;              // device word: some wait timed out
+    int* hostErr = nullptr;          // pinned, 16 words: [0] a launch failed, [1 + s] the launch of deferred step s did (sticky until rearm)
+    unsigned seq = 0;                // the next tag; 0: the tagged buffers have not been cleared yet
+    std::vector<std::pair<void*, size_t>> tagged;
+    OnchipGuard() {
+        if (const char* e = getenv("OPT_AMD_ONCHIP")) enabled = atoi(e) != 0;
+        if (const char* e = getenv("OPT_AMD_ONCHIP_ROWS")) forceRows = std::max(0, atoi(e));
+        if (const char* e = getenv("OPT_AMD_ONCHIP_WAVES")) forceWaves = std::max(0, atoi(e));
+        if (const char* e = getenv("OPT_AMD_ONCHIP_FAIL_AT")) failAt = atoi(e);
+        if (const char* e = getenv("OPT_AMD_ONCHIP_FAIL_LAUNCH")) failLaunch = atoi(e);
+        if (const char* e = getenv("OPT_AMD_ONCHIP_TIMEOUT_MS")) timeoutTicks = std::max(1, atoi(e)) * 100000LL;
+    }
+    ~OnchipGuard() {
+        for (auto& b : tagged) (void)hipFree(b.first);
+        if (bad) { (void)hipFree(bad); (void)hipHostFree(hostErr); }
+    }
+    OnchipGuard(const OnchipGuard&) = delete;
+    OnchipGuard& operator=(const OnchipGuard&) = delete;
+    bool usable() const { return enabled && !failed; }
+    const char* whyOff() const { return !enabled ? "switched off" : failed ? "a wait timed out earlier" : nullptr; }      // (describe's why_not_on_chip)
+    void allocWords(hipStream_t s) {      // (once; `bad` is cleared in stream order)
+        if (bad) return;
+        HIP_CHECK(hipMalloc((void**)&bad, sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&hostErr, 16 * sizeof(int))); for (int i = 0; i < 16; ++i) hostErr[i] = 0;
+        HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), s));
+    }
+    template <class P> P* allocTagged(size_t bytes) {      // a buffer of tagged words: cleared whenever the tags start over, freed with the guard
+        void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes));
+        tagged.push_back({p, bytes});
+        return (P*)p;
+    }
+    void clearTagged(hipStream_t s) { for (auto& b : tagged) HIP_CHECK(hipMemsetAsync(b.first, 0, b.second, s)); seq = 2; }
+    // The first of n fresh tags.  Zero = no tag, and tags never repeat on a buffer: the buffers are cleared before their first use and long before the counter wraps.
+    unsigned tags(unsigned n, hipStream_t s) {
+        if (seq == 0 || (unsigned long long)seq + n > 0xE0000000u) clearTagged(s);
+        seq += n;
+        return seq - n;
+    }
+    int failAtThisLaunch() { const int f = (failLaunch < 0 || launches == failLaunch) ? failAt : -1; ++launches; return f; }
+    OcTimeouts timeouts(int L, bool crossProcess) const { return ocTimeouts(timeoutTicks, L, crossProcess); }
+    // After the stream has drained: did the last launch fail?  Consumes the answer; a failure switches the path off until rearm().
+    bool failedNow() {
+        if (!launched) return false;
+        launched = false;
+        if (__atomic_load_n(hostErr, __ATOMIC_ACQUIRE) == 0) return false;
+        failed = true;
+        return true;
+    }
+    bool failedPeek() const { return launched && hostErr && __atomic_load_n(hostErr, __ATOMIC_ACQUIRE) != 0; }      // the same question, the answer not consumed
+    void rearm(hipStream_t s) {      // the back-off is over: clear the failure state so that the next solve launches again (stream-ordered)
+        failed = false;
+        if (!bad) return;
+        clearStepSlots(); __atomic_store_n(hostErr, 0, __ATOMIC_RELEASE);
+        HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), s));
+    }
+    // Deferred steps (PcgSolver inside Opt_ProblemSolve): the guarded update of each gets a word of its own, so that the host can tell afterwards WHICH step's solve gave up
+    void setStepSlot(int slot) { stepSlot = (slot >= 0 && slot < 15) ? slot : -1; }
+    int* stepWord() const { return stepSlot >= 0 ? hostErr + 1 + stepSlot : nullptr; }
+    bool stepFailed(int slot) const { return hostErr && slot >= 0 && slot < 15 && __atomic_load_n(hostErr + 1 + slot, __ATOMIC_ACQUIRE) != 0; }
+    void clearStepSlots() { if (hostErr) for (int i = 1; i < 16; ++i) __atomic_store_n(hostErr + i, 0, __ATOMIC_RELEASE); }
+};
+
+namespace {
+
+typedef unsigned long long oc_u64;
 
 // SYS: words that cross GPUs (the peer window: uncached memory, system scope); else agent scope
 template <bool SYS = false> __device__ __forceinline__ oc_u64 ocLoad(const oc_u64* p) {

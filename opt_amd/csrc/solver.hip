@@ -12,6 +12,7 @@
 //  * alphaNumerator <- betaNumerator (a D2D memcpy per iteration in the reference, :1091) is a two-slot
 //    rotation written by workgroup 0 of Step3.
 #include "solver.h"
+#include "onchip_sync.h"
 #include <chrono>
 #include <mutex>
 #include <cmath>
@@ -375,6 +376,10 @@ struct PcgSolver : SolverBase {
         scal4[0] = scal + 8; scal4[1] = scal + 12;
         HIP_CHECK(hipHostMalloc((void**)&hostBuf, 2 * kMaxPartials * sizeof(double)));      // room for two reductions read in one go (LM: model cost + new cost)
         E->slab = Slab{};
+        chip = E->onChipGuard();
+        hipDevice_t streamDev = 0; HIP_CHECK(hipStreamGetDevice(stream, &streamDev));
+        static std::timed_mutex leases[64];
+        lease = &leases[(unsigned)streamDev % 64u];
     }
     ~PcgSolver() override {
         (void)hipStreamSynchronize(stream);
@@ -402,12 +407,30 @@ struct PcgSolver : SolverBase {
     // (ii) A foreign tenant (another process, another library's long kernel) is caught by the kernel itself: the waits of its FIRST phase are bounded by
     //      10 ms (firstTicks) -- every workgroup posts its words before it waits, so passing that wait proves the grid resident; nothing has been written by then.
     // (iii) After a time-out the step is redone by the streaming kernels and the plan stays on them for `onChipBackoff` clean steps (8, then 16, 32 ... 1024), then
-    //      tries the chip again (EnergyOps::onChipRearm): a tenant that has left does not cost the plan its fast path for life.
-    static std::timed_mutex& chipLease() { static std::timed_mutex m[64]; int dev = 0; (void)hipGetDevice(&dev); return m[(unsigned)dev % 64u]; }
+    //      tries the chip again (OnchipGuard::rearm): a tenant that has left does not cost the plan its fast path for life.
+    // The lease is the mutex of the device the plan's stream was created on, resolved once in the constructor (the caller may switch devices between a step's lock and
+    // its unlock).  Inside Opt_ProblemSolve it is held across the deferred steps until they are settled.
+    std::timed_mutex* lease = nullptr;
     bool leaseHeld = false;
-    bool takeLease() { if (leaseHeld) return true; leaseHeld = chipLease().try_lock_for(std::chrono::milliseconds(50)); return leaseHeld; }
-    void dropLease() { if (leaseHeld) { chipLease().unlock(); leaseHeld = false; } }
+    bool takeLease() { if (leaseHeld) return true; leaseHeld = lease->try_lock_for(std::chrono::milliseconds(50)); return leaseHeld; }
+    void dropLease() { if (leaseHeld) { lease->unlock(); leaseHeld = false; } }
+    OnchipGuard* chip = nullptr;      // the kernel set's on-chip time-out protocol (EnergyOps::onChipGuard), or nullptr: the plan never runs on chip
     int onChipFailures = 0, onChipBackoff = 0, onChipCleanSteps = 0;
+    bool onChipOff() const { return chip && chip->failed; }      // a wait timed out: the plan is on the streaming kernels until the back-off is over
+    // An on-chip solve gave up (its failure word consumed): count it, set the back-off, say so (the first three times) -- `redo` is what happens to the step.
+    void onChipFailure(const char* redo) {
+        dropLease();      // the launch has left the chip
+        chip->failed = true;
+        ++onChipFailures; onChipCleanSteps = 0; onChipBackoff = std::min(8 << std::min(onChipFailures - 1, 7), 1024);
+        if (onChipFailures <= 3)
+            fprintf(stderr, "Opt(amd): a wait inside the on-chip PCG kernel timed out (its workgroups were not co-resident: is the GPU shared?); %s "
+                            "with the streaming kernels and the plan stays on them for %d steps before it tries the chip again\n", redo, onChipBackoff);
+        lastStepOnChip = false; usedOnChip = false;
+    }
+    // a step on the streaming kernels has ended: the back-off is over after onChipBackoff of them, and the next step tries the chip again
+    void onChipCleanStep() {
+        if (onChipOff() && ++onChipCleanSteps >= onChipBackoff) chip->rearm(stream);
+    }
     bool boundForSolve = false;      // bind() has run inside the current Opt_ProblemSolve (SolverBase::insideSolve)
     bool jtfReady = false;           // the pass that computed the last step's cost also ran this step's PCGInit1 (EnergyOps::evalCostAndJTFInit; only inside Opt_ProblemSolve)
     // Deferred Gauss-Newton steps (inside Opt_ProblemSolve, kernel sets with evalCostAndJTFInit): nothing a step computes steers the next one -- the cost is only reported --
@@ -460,10 +483,10 @@ struct PcgSolver : SolverBase {
     struct PendingStep { int slot, step; bool onChip; };
     std::vector<PendingStep> pendingSteps;
     Reduction costRing[kDefer];
-    bool onChipAllowed() const { return onChipOk && sp.amd_onchip != 0 && sp.amd_reference_order == 0; }
+    bool onChipAllowed() const { return !onChipOff() && sp.amd_onchip != 0 && sp.amd_reference_order == 0; }
     bool singleKernelAllowed() const { return oneKernel && sp.amd_reference_order == 0; }
     double* lmBreak = nullptr;          // pinned: {iteration + 1, zeta} of an on-chip LM solve's q early-out (OnChipLm::breakInfo)
-    bool onChipOk = true, usedOnChip = false, onChipFellBack = false, lastStepOnChip = false; double* onChipTrace = nullptr; int onChipTraceCap = 0;      // EnergyOps::pcgSolveOnChip
+    bool usedOnChip = false, lastStepOnChip = false; double* onChipTrace = nullptr; int onChipTraceCap = 0;      // EnergyOps::pcgSolveOnChip
     // true iff `mine` holds on every rank: one all-reduce of a count and one read-back (once per Gauss-Newton step in slab mode)
     bool allRanksAgree(bool mine) {
         hostBuf[0] = mine ? 0.0 : 1.0;
@@ -894,7 +917,7 @@ struct PcgSolver : SolverBase {
         exchangeUnknowns();
         E->precompute(ctx);
         // (inside Opt_ProblemSolve the first step follows at once on the same unknowns: its PCGInit1 rides on this cost pass where the kernel set can -- see stepOnce)
-        jtfReady = false; pendingSteps.clear(); E->onChipStepSlot(-1);
+        jtfReady = false; pendingSteps.clear(); if (chip) chip->setStepSlot(-1);
         if (!lm && !distributed && insideSolve && E->bindInvariantDuringSolve() && sp.nIterations > 0 && singleKernelAllowed() && r2 && sp.lIterations > 0 &&
             E->evalCostAndJTFInit(redCH, r, p, delta, nPad, redC, ctx)) { jtfReady = true; prevCost = (T)hostSum(redCH); }
         else prevCost = computeCost();
@@ -947,25 +970,20 @@ struct PcgSolver : SolverBase {
     int settlePending() {
         int failed = -1;
         for (const PendingStep& ps : pendingSteps) {
-            if (ps.onChip && E->onChipStepFailed(ps.slot)) { failed = ps.step; break; }
+            if (ps.onChip && chip->stepFailed(ps.slot)) { failed = ps.step; break; }
             double c = 0; for (int i = 0; i < costRing[ps.slot].n; ++i) c += costRing[ps.slot].partials[i];
             if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)(T)c);
             prevCost = (T)c; lastStepOnChip = ps.onChip;
         }
         pendingSteps.clear();
-        E->onChipClearStepSlots();
+        if (chip) chip->clearStepSlots();
         return failed;
     }
     // The deferred step `f` found its on-chip solve timed out: nothing has been applied from it on (the flag is sticky: later launches return at once and every guarded
     // update is skipped), so the solve goes back to step f on the streaming kernels.  r, p of the newest cost + PCGInit1 pass belong to exactly those unknowns.
     void rewindTo(int f) {
-        (void)E->onChipFailed();      // (consumes the launch's failure word)
-        dropLease();
-        ++onChipFailures; onChipCleanSteps = 0; onChipBackoff = std::min(8 << std::min(onChipFailures - 1, 7), 1024);
-        if (onChipFailures <= 3)
-            fprintf(stderr, "Opt(amd): a wait inside the on-chip PCG kernel timed out (its workgroups were not co-resident: is the GPU shared?); the solve goes back to that step "
-                            "with the streaming kernels and the plan stays on them for %d steps before it tries the chip again\n", onChipBackoff);
-        onChipOk = false; onChipFellBack = true; lastStepOnChip = false; usedOnChip = false;
+        (void)chip->failedNow();      // (consumes the launch's failure word)
+        onChipFailure("the solve goes back to that step");
         sp.nIter = f;
     }
     int stepOnce(void** params, bool& again) {
@@ -981,7 +999,7 @@ struct PcgSolver : SolverBase {
         }
         if (sp.nIter >= sp.nIterations) { cleanup(); return 0; }
         const int deferSlot = mayDefer ? (int)pendingSteps.size() : -1;
-        E->onChipStepSlot(deferSlot);
+        if (chip) chip->setStepSlot(deferSlot);
         bool deferredNow = false;
         const T* preArg = E->usePreconditioner ? preconditioner : nullptr;   // solver.t:467-470: pre = 1 unless the energy preconditions
 
@@ -1126,7 +1144,7 @@ struct PcgSolver : SolverBase {
             if (lm && !distributed) {
                 E->evalCost(redCH, ctx);                   // both sets of partials are written straight to pinned memory: one drain, no copy kernels
                 drain();
-                if (usedOnChip && verbosity > 0 && lmBreak && lmBreak[0] > 0.0 && !E->onChipFailedPeek()) { printf("zeta=%.18g, breaking at iteration: %d\n", lmBreak[1], (int)lmBreak[0] - 1); lmBreak[0] = 0.0; }
+                if (usedOnChip && verbosity > 0 && lmBreak && lmBreak[0] > 0.0 && !chip->failedPeek()) { printf("zeta=%.18g, breaking at iteration: %d\n", lmBreak[1], (int)lmBreak[0] - 1); lmBreak[0] = 0.0; }
                 double sm = 0, sc = 0;
                 for (int i = 0; i < redMH.n; ++i) sm += redMH.partials[i];
                 for (int i = 0; i < redCH.n; ++i) sc += redCH.partials[i];
@@ -1162,10 +1180,7 @@ struct PcgSolver : SolverBase {
             pendingSteps.push_back({deferSlot, sp.nIter, usedOnChip});
             usedOnChip = false;
             sp.nIter += 1;
-            if (!onChipOk && onChipFailures > 0 && ++onChipCleanSteps >= onChipBackoff) {      // back-off over (these were streaming steps): the next step tries the chip again
-                onChipOk = true; onChipFellBack = false;
-                E->onChipRearm(ctx);
-            }
+            onChipCleanStep();
             return 1;
         }
         if (!pendingSteps.empty()) {      // the stream has drained (this step's cost was read): what the deferred steps before it left
@@ -1183,14 +1198,10 @@ struct PcgSolver : SolverBase {
         lastStepOnChip = usedOnChip;
         if (usedOnChip) {      // (the stream has drained: the cost was read)
             usedOnChip = false;
-            bool ocFailedNow = E->onChipFailed();
-            dropLease();      // the launch has left the chip
-            if (ocFailedNow) {
-                ++onChipFailures; onChipCleanSteps = 0; onChipBackoff = std::min(8 << std::min(onChipFailures - 1, 7), 1024);
-                if (onChipFailures <= 3)
-                    fprintf(stderr, "Opt(amd): a wait inside the on-chip PCG kernel timed out (its workgroups were not co-resident: is the GPU shared?); this linear solve is redone "
-                                    "with the streaming kernels and the plan stays on them for %d steps before it tries the chip again\n", onChipBackoff);
-                onChipOk = false; onChipFellBack = true; lastStepOnChip = false; unknownsUpdated = false;
+            if (!chip->failedNow()) dropLease();      // the launch has left the chip
+            else {
+                onChipFailure("this linear solve is redone");
+                unknownsUpdated = false;
                 if (lm) {      // the kernel produced no delta: the update above added nothing meaningful -- back to the saved unknowns, then the launch-per-iteration loop
                     imageOp(2);
                     E->precompute(ctx);      // (workgroups that had finished before the others gave up may have written their delta: the update above was then not the identity)
@@ -1241,10 +1252,7 @@ struct PcgSolver : SolverBase {
             prevCost = newCost;
         }
         sp.nIter += 1;
-        if (!onChipOk && onChipFailures > 0 && ++onChipCleanSteps >= onChipBackoff) {      // back-off over: the next step tries the chip again
-            onChipOk = true; onChipFellBack = false;
-            E->onChipRearm(ctx);
-        }
+        onChipCleanStep();
         return 1;
     }
 
@@ -1257,13 +1265,13 @@ struct PcgSolver : SolverBase {
     }
     long numUnknownScalars() const override { return n; }
     double trustRegionRadius() const override { return (double)trust_region_radius; }
-    int onChipStatus() const override { return onChipFellBack ? 2 : lastStepOnChip ? 1 : 0; }
+    int onChipStatus() const override { return onChipOff() ? 2 : lastStepOnChip ? 1 : 0; }
     std::string describe() override {
         std::string d = sp.amd_reference_order ? std::string("path=reference-order (PCGStep1 [+ the previous PCGStep3] and PCGStep2 per PCG iteration, r / z / A p in memory); amd_reference_order=1")
                                                : E->describe(sp.lIterations, lm);
         if (!sp.amd_reference_order && !sp.amd_onchip) d += "; amd_onchip=0";
         if (!sp.amd_reference_order && !oneKernel) d += "; OPT_AMD_ONEKERNEL=0 (reference-order loop by environment)";
-        if (onChipFailures) d += "; onchip_fallbacks=" + std::to_string(onChipFailures) + "; onchip_backoff_steps_left=" + std::to_string(onChipOk ? 0 : onChipBackoff - onChipCleanSteps);
+        if (onChipFailures) d += "; onchip_fallbacks=" + std::to_string(onChipFailures) + "; onchip_backoff_steps_left=" + std::to_string(onChipOff() ? onChipBackoff - onChipCleanSteps : 0);
         // what Opt_ProblemSolve does beyond Init + Step by Step on this plan, and where the trial over delta's placement stands
         if (!lm && !distributed && E->supportsDeferredSteps()) d += "; solve_enqueues_steps_back_to_back=up to " + std::to_string(kDefer - 1);
         if (!lm && !distributed && E->deltaMovable() && nPad * sizeof(T) >= ((size_t)64 << 20))

@@ -334,24 +334,13 @@ __global__ __launch_bounds__(kBlock) void march_applyDelta(T* __restrict__ X, co
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) X[i] = X[i] + delta[i];
 }
 
-// Host side: buffers, variant choice, launch, the time-out verdict.  OPT_AMD_ONCHIP=0 switches the path off (the one A/B switch); OPT_AMD_ONCHIP_ROWS / _WAVES force a
-// variant (tests run every variant on small images); OPT_AMD_ONCHIP_FAIL_AT / _TIMEOUT_MS: the time-out path's test hooks.
+// Host side: buffers, variant choice, launch.  The switches (OPT_AMD_ONCHIP*) and the time-out verdict: `guard` (onchip_sync.h OnchipGuard).
 template <class T>
 struct OnchipMarch {
-    bool enabled = true, failed = false, launched = false;
-    int forceRows = 0, forceWaves = 0, failAt = -1; long long timeoutTicks = 0;      // 0: onchip_sync.h ocTimeouts() decides; OPT_AMD_ONCHIP_TIMEOUT_MS overrides
-    oc_u64 *slots = nullptr, *box = nullptr; int *bad = nullptr, *hostErr = nullptr; unsigned seq = 0; size_t slotBytes = 0, boxBytes = 0;
-    int lastRows = 0, lastWaves = 0, lastG = 0;
-    OnchipMarch() {
-        if (const char* e = getenv("OPT_AMD_ONCHIP")) enabled = atoi(e) != 0;
-        if (const char* e = getenv("OPT_AMD_ONCHIP_ROWS")) forceRows = std::max(0, atoi(e));
-        if (const char* e = getenv("OPT_AMD_ONCHIP_WAVES")) forceWaves = std::max(0, atoi(e));
-        if (const char* e = getenv("OPT_AMD_ONCHIP_FAIL_AT")) failAt = atoi(e);
-        if (const char* e = getenv("OPT_AMD_ONCHIP_TIMEOUT_MS")) timeoutTicks = std::max(1, atoi(e)) * 100000LL;
-    }
-    ~OnchipMarch() { if (slots) (void)hipFree(slots); if (box) (void)hipFree(box); if (bad) (void)hipFree(bad); if (hostErr) (void)hipHostFree(hostErr); }
+    OnchipGuard guard;
+    oc_u64 *slots = nullptr, *box = nullptr;      // the tagged buffers
     // The buffers of the path, sized for the plan's image (the dimensions of a plan are fixed).  Called when the plan is made (the kernel set's constructor), so that the
-    // first linear solve of a plan does not pay for four allocations; solve() calls it itself if nobody has.  zero = no tag.
+    // first linear solve of a plan does not pay for four allocations; solve() calls it itself if nobody has.
     // ... only for plans that can take the path at all: some variant of THIS operator fits THIS device's CUs for the image (a 4-channel double image of
     // 1-2 M pixels used to allocate ~256 MB of tagged box it could never use)
     template <class Op> void reserveFor(int W, int H, int cus) {
@@ -359,13 +348,11 @@ struct OnchipMarch {
         if (select<Op, false>(W, H, cus, sx, ty, G) || select<Op, true>(W, H, cus, sx, ty, G)) reserve(W, H, Op::C);
     }
     void reserve(int W, int H, int C) {
-        if (slots || !enabled || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return;
+        if (slots || !guard.enabled || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return;
         if ((long)W * H > (long)kMoMaxG * 8 * kMoSpan * 16 || divUp(W, kMoSpan) > kMoMaxG * 8) return;      // (more pixels than the largest variant holds on the largest grid: the path will never be taken)
-        slotBytes = sizeof(oc_u64) * 2 * (size_t)kMoMaxG * kMoNWMax; boxBytes = sizeof(oc_u64) * 2 * (size_t)W * H * C * (sizeof(T) / 4);
-        HIP_CHECK(hipMalloc((void**)&slots, slotBytes)); HIP_CHECK(hipMalloc((void**)&box, boxBytes));
-        HIP_CHECK(hipMalloc((void**)&bad, sizeof(int))); HIP_CHECK(hipHostMalloc((void**)&hostErr, 64)); *hostErr = 0;
-        HIP_CHECK(hipMemset(bad, 0, sizeof(int))); HIP_CHECK(hipMemset(slots, 0, slotBytes)); HIP_CHECK(hipMemset(box, 0, boxBytes)); HIP_CHECK(hipStreamSynchronize(nullptr));      // (done before the plan's own stream sees the buffers)
-        seq = 2;
+        slots = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)kMoMaxG * kMoNWMax);
+        box = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)W * H * C * (sizeof(T) / 4));
+        guard.allocWords(nullptr); guard.clearTagged(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr));      // (done before the plan's own stream sees the buffers)
     }
     struct Variant { int rows, waves; const void* fn; };
     template <class Op, int R, int WV, bool LM> static constexpr size_t ldsBytes() {      // A p and delta (where they wait in LDS) + b (LM) + the sums' staging
@@ -393,8 +380,8 @@ struct OnchipMarch {
         stripsX = divUp(W, kMoSpan);
         const Variant* best = nullptr; int bestCost = 1 << 30;
         for (const auto& v : variants<Op, LM>()) {
-            if (forceRows && v.rows != forceRows) continue;
-            if (forceWaves && v.waves != forceWaves) continue;
+            if (guard.forceRows && v.rows != guard.forceRows) continue;
+            if (guard.forceWaves && v.waves != guard.forceWaves) continue;
             const int ty = divUp(H, v.rows), g = divUp(stripsX * ty, v.waves);
             if (g > std::min(cus, kMoMaxG)) continue;
             const int cost = (v.waves == 4 ? 100 : 136) * (v.rows + 2);      // (measured: two waves per SIMD march a row pair in 1.36 of the time one wave marches a row)
@@ -403,59 +390,43 @@ struct OnchipMarch {
         return best;
     }
     // the whole linear solve + X += delta; false (nothing touched): not offered for this plan
-    // lm: Levenberg-Marquardt (the solver applies the update itself and hears of a time-out through hostErr)
+    // lm: Levenberg-Marquardt (the solver applies the update itself and hears of a time-out through the guard's hostErr)
     template <class Op> bool solve(const Op& op, int W, int H, const uint8_t* flags, const T* coef, const T* r0, const T* p0, T* delta, T* X, int L, int cus, LaunchCtx& ctx,
                                    const OnChipLm<T>* lm = nullptr) {
         constexpr int C = Op::C;
-        if (!enabled || failed || L <= 0 || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return false;
+        if (!guard.usable() || L <= 0 || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return false;
         if (lm && (!lm->CtC || lm->resetPeriod < L)) return false;      // a split residual reset before the last iteration: the generic kernels' business
         int stripsX = 0, tilesY = 0, G = 0;
         const Variant* V = lm ? select<Op, true>(W, H, cus, stripsX, tilesY, G) : select<Op, false>(W, H, cus, stripsX, tilesY, G);
         if (!V) return false;
-        if (!slots) { reserve(W, H, C); if (!slots) return false; HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream)); }
-        if (seq > 0xE0000000u || seq + (unsigned)L > 0xE0000000u) {      // tags never repeat: start over on cleared buffers long before the counter wraps
-            HIP_CHECK(hipMemsetAsync(slots, 0, slotBytes, ctx.stream)); HIP_CHECK(hipMemsetAsync(box, 0, boxBytes, ctx.stream));
-            seq = 2;
-        }
-        const OcTimeouts tmo = ocTimeouts(timeoutTicks, L, false);
-        MoArgs<T> K{W, H, r0, p0, delta, flags, coef, stripsX, tilesY, G, L, seq, slots, box, bad, tmo.later, failAt, tmo.first, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0), (lm || !X) ? hostErr : nullptr, lm ? lm->breakInfo : nullptr};      // (no X: the solver applies the update itself, as for LM)
+        if (!slots) { reserve(W, H, C); if (!slots) return false; }
+        const unsigned tag0 = guard.tags((unsigned)L, ctx.stream);
+        const OcTimeouts tmo = guard.timeouts(L, false);
+        MoArgs<T> K{W, H, r0, p0, delta, flags, coef, stripsX, tilesY, G, L, tag0, slots, box, guard.bad, tmo.later, guard.failAtThisLaunch(), tmo.first, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0),
+                    (lm || !X) ? guard.hostErr : nullptr, lm ? lm->breakInfo : nullptr};      // (no X: the solver applies the update itself, as for LM)
         {
             ScopedKernel k(ctx, "PCGSolveOnChip");
             Op opc = op;
             void* kargs[] = {(void*)&opc, (void*)&K};
-            if (hipLaunchKernel(V->fn, dim3(G), dim3(V->waves * kWave), kargs, 0, ctx.stream) != hipSuccess) { (void)hipGetLastError(); enabled = false; return false; }
+            if (hipLaunchKernel(V->fn, dim3(G), dim3(V->waves * kWave), kargs, 0, ctx.stream) != hipSuccess) { (void)hipGetLastError(); guard.enabled = false; return false; }
         }
-        seq += (unsigned)L;
         if (!lm && X) {
             ScopedKernel k(ctx, "PCGLinearUpdate");
             const long n = (long)W * H * C;
             const int grid = (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, (long)cus * 8));
-            march_applyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(X, delta, n, bad, hostErr);
+            march_applyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(X, delta, n, guard.bad, guard.hostErr);
         }
-        launched = true; lastRows = V->rows; lastWaves = V->waves; lastG = G;
+        guard.launched = true;
         return true;
-    }
-    bool failedNow() {
-        if (!launched) return false;
-        launched = false;
-        if (__atomic_load_n(hostErr, __ATOMIC_ACQUIRE) == 0) return false;
-        failed = true;
-        return true;
-    }
-    bool failedPeek() const { return launched && hostErr && __atomic_load_n(hostErr, __ATOMIC_ACQUIRE) != 0; }      // EnergyOps::onChipFailedPeek
-    void rearm(LaunchCtx& ctx) {      // EnergyOps::onChipRearm
-        if (!bad) return;
-        failed = false; __atomic_store_n(hostErr, 0, __ATOMIC_RELEASE);
-        HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
     }
     template <class Op> std::string describe(int W, int H, int cus, int L, bool lmv, const char* marchName) const {
         int stripsX = 0, tilesY = 0, G = 0;
-        const Variant* V = (enabled && !failed && L > 0) ? (lmv ? select<Op, true>(W, H, cus, stripsX, tilesY, G) : select<Op, false>(W, H, cus, stripsX, tilesY, G)) : nullptr;
+        const Variant* V = (guard.usable() && L > 0) ? (lmv ? select<Op, true>(W, H, cus, stripsX, tilesY, G) : select<Op, false>(W, H, cus, stripsX, tilesY, G)) : nullptr;
         char buf[500];
         if (V) snprintf(buf, sizeof buf, "path=on-chip (march_onchipPcg%s); onchip_rows_per_wave=%d; waves_per_workgroup=%d; wave_tiles=%dx%d of 62 x %d pixels; workgroups=%d of %d CUs; fallback=one launch per PCG iteration (%s)",
                         lmv ? ", LM while lIterations <= residual_reset_period" : "", V->rows, V->waves, stripsX, tilesY, V->rows, G, cus, lmv ? "generic kernels" : marchName);
         else snprintf(buf, sizeof buf, "path=one launch per PCG iteration (%s); why_not_on_chip=%s", lmv ? "generic kernels, LM" : marchName,
-                      !enabled ? "switched off" : failed ? "a wait timed out earlier" : "the wave tiles do not fit the CUs");
+                      guard.whyOff() ? guard.whyOff() : "the wave tiles do not fit the CUs");
         return buf;
     }
 };

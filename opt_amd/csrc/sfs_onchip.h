@@ -16,7 +16,7 @@
 //           partial sums as tagged words and adds ALL workgroups' words in workgroup order: the same bits everywhere, so alpha, beta and the q early-out
 //           (solver.t:1093-1102) agree on the whole grid without a broadcast.  One grid-wide wait per iteration.
 // Levenberg-Marquardt: + CtC p (o.t:2076-2082); Q_k = 1/2 sum delta . (r + b) (:483-485) is formed where iteration k is applied and travels with the sums of
-// iteration k + 1 -- exactly the hand-over of the launch-per-iteration loop (solver.hip runSingleKernelLoopLM), so an early-out leaves the reference's delta.
+// iteration k + 1 -- exactly the hand-over of the launch-per-iteration loop (solver.hip runLaunchPerIterationLM), so an early-out leaves the reference's delta.
 // A split residual reset in the MIDDLE of a linear solve (lIterations > residual_reset_period) is not offered: the host keeps such solves on sfs_pcgMarch.
 // Every wait is bounded by the device's wall clock; a time-out raises `bad`, every workgroup leaves the loop at its next sum, nothing is written to delta and the
 // host redoes the linear solve with the marching kernels.  The grid must be co-resident (one workgroup per CU): the launcher checks workgroups <= CUs.

@@ -320,8 +320,8 @@ struct PcgSolver : SolverBase {
     bool oneKernelLM = true;            // OPT_AMD_ONEKERNEL_LM=0: the same switch for the Levenberg-Marquardt loop only
     Reduction setS[2][4];               // ping-pong {alphaNum, alphaDen, s2, s3} of the single-kernel iteration
     bool unknownsUpdated = false;       // this step's PCGLinearUpdate was folded into the end of the PCG loop (EnergyOps::finishUpdate)
-    bool keepReferenceP = false;        // run the (dead) last PCGStep3 so that `p` matches the reference after a step
-    std::vector<void*> allocs;
+    std::vector<void*> allocs;          // device memory (allocVec, allocRed)
+    std::vector<void*> pinned;          // pinned host memory (allocPinned)
     Reduction redA, redB, redQ, redC;   // alpha denominator, beta numerator, q, cost / init numerator
     Reduction redQ2;                    // second Q buffer: the LM single-kernel loop enqueues launch k + 1 (which writes Q_k) before the host has read Q_{k-1}
     Reduction redQR;                    // pinned: Q of the split residual reset (its own buffer: the reset is enqueued while the host may still poll redQ / redQ2)
@@ -349,6 +349,10 @@ struct PcgSolver : SolverBase {
         Reduction R; HIP_CHECK(hipMalloc((void**)&R.partials, kMaxPartials * sizeof(double))); HIP_CHECK(hipMemset(R.partials, 0, kMaxPartials * sizeof(double)));
         allocs.push_back(R.partials); return R;
     }
+    void* allocPinned(size_t bytes) {
+        void* v; HIP_CHECK(hipHostMalloc(&v, bytes));
+        pinned.push_back(v); return v;
+    }
     PcgSolver(EnergyOps<T>* e, bool useLM, bool timing, int verb) : E(e), lm(useLM) {
         verbosity = verb; timer.enabled = timing;
         HIP_CHECK(hipStreamCreate(&stream));   // blocking stream: ordered against the caller's null-stream work
@@ -362,7 +366,6 @@ struct PcgSolver : SolverBase {
         if (lm) { b = allocVec(); Adelta = allocVec(); SSq = allocVec(); prevX = allocVec(); }
         p2 = allocVec();
         if (const char* e = getenv("OPT_AMD_ONEKERNEL")) oneKernel = atoi(e) != 0;
-        if (const char* e = getenv("OPT_AMD_DELTA_TRIAL")) trialMode = atoi(e);
         if (const char* e = getenv("OPT_AMD_ONEKERNEL_LM")) oneKernelLM = atoi(e) != 0;
         r2 = allocVec(); Ap2 = allocVec();                // second r / A p buffers of the single-kernel iterations (kernels that keep A p in memory read the old one on a halo)
         for (auto& st : setS) for (auto& R : st) R = allocRed();
@@ -370,11 +373,11 @@ struct PcgSolver : SolverBase {
         // Q (solver.t:483-485, 1093-1102) is read by the host once per LM iteration and by no kernel: its partials go straight to pinned host memory
         // (<= 16 KB of posted writes per launch) instead of through a device buffer and a copy kernel per iteration (830 copyBuffer launches, 7 % of config 3's GPU time)
         // With the single-kernel loop each partial is two tagged words (2 x kMaxPartials slots), which the host polls: no event packet in the stream either.
-        for (Reduction* R : {&redQ, &redQ2, &redQR, &redMH, &redCH}) { HIP_CHECK(hipHostMalloc((void**)&R->partials, 2 * kMaxPartials * sizeof(double))); memset(R->partials, 0, 2 * kMaxPartials * sizeof(double)); R->hostVisible = true; }
-        HIP_CHECK(hipHostMalloc((void**)&stampFlag, 64)); *stampFlag = 0;
+        for (Reduction* R : {&redQ, &redQ2, &redQR, &redMH, &redCH}) { R->partials = (double*)allocPinned(2 * kMaxPartials * sizeof(double)); memset(R->partials, 0, 2 * kMaxPartials * sizeof(double)); R->hostVisible = true; }
+        stampFlag = (unsigned long long*)allocPinned(64); *stampFlag = 0;
         HIP_CHECK(hipMalloc((void**)&scal, 16 * sizeof(double))); HIP_CHECK(hipMemset(scal, 0, 16 * sizeof(double))); allocs.push_back(scal);
         scal4[0] = scal + 8; scal4[1] = scal + 12;
-        HIP_CHECK(hipHostMalloc((void**)&hostBuf, 2 * kMaxPartials * sizeof(double)));      // room for two reductions read in one go (LM: model cost + new cost)
+        hostBuf = (double*)allocPinned(2 * kMaxPartials * sizeof(double));      // room for two reductions read in one go (LM: model cost + new cost)
         E->slab = Slab{};
         chip = E->onChipGuard();
         hipDevice_t streamDev = 0; HIP_CHECK(hipStreamGetDevice(stream, &streamDev));
@@ -385,18 +388,10 @@ struct PcgSolver : SolverBase {
         (void)hipStreamSynchronize(stream);
         dropLease();
         for (void* a : allocs) (void)hipFree(a);
-        if (hostBuf) (void)hipHostFree(hostBuf);
-        if (redQ.partials) (void)hipHostFree(redQ.partials);
-        if (redQ2.partials) (void)hipHostFree(redQ2.partials);
-        if (redMH.partials) (void)hipHostFree(redMH.partials);
-        if (redQR.partials) (void)hipHostFree(redQR.partials);
-        if (stampFlag) (void)hipHostFree(stampFlag);
-        if (lmBreak) (void)hipHostFree(lmBreak);
+        for (void* a : pinned) (void)hipHostFree(a);
         if (onChipTrace) (void)hipFree(onChipTrace);
-        if (redCH.partials) (void)hipHostFree(redCH.partials);
-        for (Reduction& R : costRing) if (R.partials) (void)hipHostFree(R.partials);
-        for (hipEvent_t e : trialEv) if (e) (void)hipEventDestroy(e);
-        if (hostBufQ) { (void)hipHostFree(hostBufQ); (void)hipEventDestroy(qEvent); }
+        deltaTrial.destroyEvents();
+        if (qEvent) (void)hipEventDestroy(qEvent);
         (void)hipStreamDestroy(stream);
     }
 
@@ -433,52 +428,64 @@ struct PcgSolver : SolverBase {
     }
     bool boundForSolve = false;      // bind() has run inside the current Opt_ProblemSolve (SolverBase::insideSolve)
     bool jtfReady = false;           // the pass that computed the last step's cost also ran this step's PCGInit1 (EnergyOps::evalCostAndJTFInit; only inside Opt_ProblemSolve)
-    // Deferred Gauss-Newton steps (inside Opt_ProblemSolve, kernel sets with evalCostAndJTFInit): nothing a step computes steers the next one -- the cost is only reported --
-    // so up to kDefer - 1 steps are enqueued back to back and their costs (one pinned partials buffer each) and on-chip verdicts (one word each) are read at the next drain.
     // Where delta lives (round 6).  delta is the one vector the Gauss-Newton loop reads AND writes, and the time of a launch follows the region the allocator put it in
     // (profiles/NOTES.md: 173 / 176 / 191 us at 4096^2 for the same binary in one process, region by region; the ring, the flag bytes and the caller's arrays do not matter).
-    // The first long linear solve of a large single-GPU plan therefore tries kTrialCands allocations of it: after launch kTrialFirst delta is copied into a fresh vector
-    // every kTrialWindow launches (a copy: no bit changes), each window is timed with one event pair, the loop goes on in the fastest and the others are freed.
+    // The first long linear solve of a large single-GPU plan therefore tries kCands allocations of it: after launch kFirst delta is copied into a fresh vector
+    // every kWindow launches (a copy: no bit changes), each window is timed with one event pair, the loop goes on in the fastest and the others are freed.
     // OPT_AMD_DELTA_TRIAL=0: off, 2: report on stderr.
-    static constexpr int kTrialCands = 4, kTrialWindow = 6, kTrialFirst = 4;
-    int trialMode = 1, trialPhase = 0, trialAttempts = 0; std::vector<T*> trialVecs; std::vector<float> trialMs; hipEvent_t trialEv[2] = {nullptr, nullptr};
-    void trialDrop(T* keep) {      // free every trial vector but `keep`
-        for (T* v : trialVecs) if (v != keep) { for (auto it = allocs.begin(); it != allocs.end(); ++it) if (*it == (void*)v) { allocs.erase(it); break; } (void)hipFree(v); }
-        trialVecs.clear(); trialMs.clear();
-    }
-    void deltaTrial(int lIter) {
-        if (lIter == 0) {
-            if (trialPhase == 1) { trialDrop(delta); trialPhase = 0; }      // the last solve ended inside the trial: it stayed where it had got to
-            if (trialPhase == 0 && trialAttempts < 2 && sp.lIterations > kTrialFirst + kTrialCands * kTrialWindow) { trialPhase = 1; ++trialAttempts; trialVecs.assign(1, delta); trialMs.clear(); }
+    struct DeltaTrial {
+        static constexpr int kCands = 4, kWindow = 6, kFirst = 4;
+        int mode = 1, phase = 0, attempts = 0; std::vector<T*> vecs; std::vector<float> ms; hipEvent_t ev[2] = {nullptr, nullptr};
+        DeltaTrial() { if (const char* e = getenv("OPT_AMD_DELTA_TRIAL")) mode = atoi(e); }
+        void destroyEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }      // (from ~PcgSolver, before the stream goes)
+        static bool applies(const PcgSolver& s) { return !s.lm && !s.distributed && s.E->deltaMovable() && s.nPad * sizeof(T) >= ((size_t)64 << 20); }
+        void drop(PcgSolver& s, T* keep) {      // free every trial vector but `keep`
+            for (T* v : vecs) if (v != keep) { for (auto it = s.allocs.begin(); it != s.allocs.end(); ++it) if (*it == (void*)v) { s.allocs.erase(it); break; } (void)hipFree(v); }
+            vecs.clear(); ms.clear();
         }
-        if (trialPhase != 1 || lIter < kTrialFirst || (lIter - kTrialFirst) % kTrialWindow != 0) return;
-        const int w = (lIter - kTrialFirst) / kTrialWindow;      // the window about to start
-        if (!trialEv[0]) { HIP_CHECK(hipEventCreate(&trialEv[0])); HIP_CHECK(hipEventCreate(&trialEv[1])); }
-        if (w > 0) {
-            float ms = 0;
-            HIP_CHECK(hipEventRecord(trialEv[1], stream)); HIP_CHECK(hipEventSynchronize(trialEv[1])); HIP_CHECK(hipEventElapsedTime(&ms, trialEv[0], trialEv[1]));
-            trialMs.push_back(ms);
-        }
-        auto moveTo = [&](T* to) { if (to != delta) { HIP_CHECK(hipMemcpyAsync(to, delta, nPad * sizeof(T), hipMemcpyDeviceToDevice, stream)); delta = to; } };
-        if (w == 0) { HIP_CHECK(hipEventRecord(trialEv[0], stream)); return; }
-        if (w < kTrialCands) {
-            T* v = nullptr;
-            if (hipMalloc((void**)&v, nPad * sizeof(T)) == hipSuccess) {
-                allocs.push_back(v); trialVecs.push_back(v);
-                moveTo(v);
-                HIP_CHECK(hipEventRecord(trialEv[0], stream));
-                return;
+        // before launch lIter of the launch-per-iteration Gauss-Newton loop: may move s.delta
+        void beforeLaunch(PcgSolver& s, int lIter) {
+            if (s.traceEnabled || !mode || phase == 2 || !applies(s)) return;
+            if (lIter == 0) {
+                if (phase == 1) { drop(s, s.delta); phase = 0; }      // the last solve ended inside the trial: it stayed where it had got to
+                if (phase == 0 && attempts < 2 && s.sp.lIterations > kFirst + kCands * kWindow) { phase = 1; ++attempts; vecs.assign(1, s.delta); ms.clear(); }
             }
-            (void)hipGetLastError();      // (no room for another: decide among those timed so far)
+            if (phase != 1 || lIter < kFirst || (lIter - kFirst) % kWindow != 0) return;
+            const int w = (lIter - kFirst) / kWindow;      // the window about to start
+            if (!ev[0]) { HIP_CHECK(hipEventCreate(&ev[0])); HIP_CHECK(hipEventCreate(&ev[1])); }
+            if (w > 0) {
+                float t = 0;
+                HIP_CHECK(hipEventRecord(ev[1], s.stream)); HIP_CHECK(hipEventSynchronize(ev[1])); HIP_CHECK(hipEventElapsedTime(&t, ev[0], ev[1]));
+                ms.push_back(t);
+            }
+            auto moveTo = [&](T* to) { if (to != s.delta) { HIP_CHECK(hipMemcpyAsync(to, s.delta, s.nPad * sizeof(T), hipMemcpyDeviceToDevice, s.stream)); s.delta = to; } };
+            if (w == 0) { HIP_CHECK(hipEventRecord(ev[0], s.stream)); return; }
+            if (w < kCands) {
+                T* v = nullptr;
+                if (hipMalloc((void**)&v, s.nPad * sizeof(T)) == hipSuccess) {
+                    s.allocs.push_back(v); vecs.push_back(v);
+                    moveTo(v);
+                    HIP_CHECK(hipEventRecord(ev[0], s.stream));
+                    return;
+                }
+                (void)hipGetLastError();      // (no room for another: decide among those timed so far)
+            }
+            int best = 0;
+            for (int i = 1; i < (int)ms.size(); ++i) if (ms[i] < ms[best]) best = i;
+            if (mode > 1) { fprintf(stderr, "Opt(amd): delta placement trial, ms per %d launches:", kWindow); for (float m : ms) fprintf(stderr, " %.3f", m); fprintf(stderr, " -> %d\n", best); }
+            moveTo(vecs[(size_t)best]);
+            HIP_CHECK(hipStreamSynchronize(s.stream));      // (the copy out of a vector about to be freed has finished)
+            drop(s, s.delta);
+            phase = 2;
         }
-        int best = 0;
-        for (int i = 1; i < (int)trialMs.size(); ++i) if (trialMs[i] < trialMs[best]) best = i;
-        if (trialMode > 1) { fprintf(stderr, "Opt(amd): delta placement trial, ms per %d launches:", kTrialWindow); for (float m : trialMs) fprintf(stderr, " %.3f", m); fprintf(stderr, " -> %d\n", best); }
-        moveTo(trialVecs[(size_t)best]);
-        HIP_CHECK(hipStreamSynchronize(stream));      // (the copy out of a vector about to be freed has finished)
-        trialDrop(delta);
-        trialPhase = 2;
-    }
+        std::string describe(const PcgSolver& s) const {
+            if (!applies(s)) return "";
+            return std::string("; delta_placement_trial=") + (!mode ? "off" : phase == 2 ? "done" : phase == 1 ? "running" : "before the first linear solve of more than 28 launches");
+        }
+    };
+    DeltaTrial deltaTrial;
+    // Deferred Gauss-Newton steps (inside Opt_ProblemSolve, kernel sets with evalCostAndJTFInit): nothing a step computes steers the next one -- the cost is only reported --
+    // so up to kDefer - 1 steps are enqueued back to back and their costs (one pinned partials buffer each) and on-chip verdicts (one word each) are read at the next drain.
     static constexpr int kDefer = 8;
     struct PendingStep { int slot, step; bool onChip; };
     std::vector<PendingStep> pendingSteps;
@@ -513,7 +520,7 @@ struct PcgSolver : SolverBase {
     }
     // The same value without draining the stream: begin enqueues the copy and an event, end waits for that event only.
     void beginHostSum(const Reduction& R) {
-        if (!hostBufQ) { HIP_CHECK(hipHostMalloc((void**)&hostBufQ, kMaxPartials * sizeof(double))); HIP_CHECK(hipEventCreateWithFlags(&qEvent, hipEventDisableTiming)); }
+        if (!hostBufQ) { hostBufQ = (double*)allocPinned(kMaxPartials * sizeof(double)); HIP_CHECK(hipEventCreateWithFlags(&qEvent, hipEventDisableTiming)); }
         if (distributed) {
             reduceAcross(&R, 1, scal + 2);
             HIP_CHECK(hipMemcpyAsync(hostBufQ, scal + 2, sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -664,52 +671,83 @@ struct PcgSolver : SolverBase {
         trace.insert(trace.end(), {(double)sp.nIter, (double)lIter, aNum, aDen, bNum, q});
     }
 
-    // ---- PCG loop as one kernel per iteration (energy.h PcgIterArgs); returns false if the energy has no such kernel ----
-    bool runSingleKernelLoop(const T* preArg) {
-        // Row slabs: the on-chip solve runs on ALL ranks or on none (their kernels wait for each other): every rank says whether it could, the communicator adds it up.
-        bool slabOnChip = false;
-        if (distributed) {
-            slabOnChip = allRanksAgree(onChipAllowed() && preArg && sp.lIterations > 0 && !traceEnabled && E->slabOnChipAvailable(sp.lIterations));
-            if (!slabOnChip && !E->slabIterationAvailable()) return false;      // (before anything is exchanged: the three-kernel loop needs r = 0 on ghost rows)
-            if (slabOnChip) {      // the kernel reads r_0, p_0 of its halo rows from the ghost rows
-                (void)takeLease();      // (agreed collectively: this rank launches whether or not another plan of this process holds the chip)
-                exchangeVector(r); exchangeVector(p);
-                // A rank whose kernel set refuses after the vote (it should not: the vote covers the communicator's capacity and error state) launches nothing; its
-                // peers' waits then time out, and the verdict below makes every rank redo the step with the streaming loop -- a library does not exit().
-                const bool refused = !E->pcgSolveOnChip(r, p, delta, sp.lIterations, nullptr, nullptr, ctx);
-                if (refused) fprintf(stderr, "Opt(amd): the slab on-chip solve was agreed on but refused by this rank's kernel set; the step will be redone by the streaming loop\n");
-                // all ranks keep their update or none does: the ranks' verdicts (0 fine / 1 a wait timed out) are all-reduced on the device, PCGLinearUpdate checks the sum
-                E->onChipVerdict(scal + 5, refused, ctx);
-                comm.allReduceSum(comm.ctx, scal + 5, 1, (void*)stream);
-                E->onChipApply(delta, scal + 5, refused, ctx);
-                usedOnChip = true; unknownsUpdated = true; return true;
-            }
+    // ---- pieces the linear-solve paths share ----------------------------------------------------------
+    void initFinish() {      // PCGInit1_Finish (solver.t:384-392, 399-419): p = M r, delta = 0 and the partial sums of r.p behind evalJTF
+        ScopedKernel k(ctx, "PCGInit1_Finish");
+        k_initFinish<T><<<streamGrid, kBlock, 0, stream>>>(r, CtC, preconditioner, p, delta, nPacks, E->usePreconditioner ? 1 : 0, E->usesGraph ? 1 : 0, redC.partials);
+        redC.n = streamGrid;
+    }
+    // the last PCGStep2 shrunk to delta += alpha p (+ what a launch left owed); alphaNumerator: aNum's partials, or aNumTotal if it has none
+    void step2Delta(const T* pv, const double* aNumTotal, const Reduction& aNum, const Reduction& aDen, const T* pOwed = nullptr, const T* aOwed = nullptr) {
+        ScopedKernel k(ctx, "PCGStep2_delta");
+        k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, delta, pv, nPacks, aNumTotal, aNum.partials, aNum.n, aDen.partials, aDen.n, pOwed, aOwed);
+    }
+    bool qEarlyOut(int k, T Q1, T Q0, T tol) {      // LM's q-based early out after k iterations (solver.t:1093-1102)
+        const T zeta = T(k) * (Q1 - Q0) / Q1;
+        if (zeta < tol && verbosity > 0) printf("zeta=%.18g, breaking at iteration: %d\n", (double)zeta, k);
+        return zeta < tol;
+    }
+    T modelCostChange(T model_cost) {      // LM's model cost as the reference prints it (solver.t:1108-1113); returns the model cost change
+        if (verbosity > 0) printf(" cost=%f \n model_cost=%f \n", (double)prevCost, (double)model_cost);
+        const T change = prevCost - model_cost;
+        if (verbosity > 0) printf(" model_cost_change=%f \n", (double)change);
+        return change;
+    }
+    [[noreturn]] void refusedMidLoop() { fprintf(stderr, "pcgIteration refused mid-loop\n"); exit(1); }      // (a kernel set refused a launch after accepting the first)
+    // One trace row of a single-kernel iteration from its sums alphaNumerator, alphaDenominator, s2 = sum M r.Ap, s3 = sum M Ap^2: the beta numerator by expansion,
+    // sum M (r - alpha Ap)^2 = rr - 2 alpha s2 + alpha^2 s3 (clamped at 0).  quarter: an energy that does not precondition starts from p_0 = r_0 / 4 (guardedInvert(1))
+    // but continues with z = r, so the first alphaNumerator is a quarter of sum r_0^2 -- which is what the expansion needs (see march_pcgIter, stencil_march.h).
+    void traceRow(int k, double aNum, double aDen, double s2, double s3, bool quarter) {
+        const T al = ((T)aDen > T(0)) ? (T)aNum / (T)aDen : T(0);
+        const double rr = quarter ? 4.0 * aNum : aNum;
+        const double bNum = std::fmax(rr - 2.0 * (double)al * s2 + (double)al * (double)al * s3, 0.0);
+        trace.insert(trace.end(), {(double)sp.nIter, (double)k, aNum, aDen, bNum, 0.0});
+    }
+
+    // Row slabs: the on-chip solve runs on ALL ranks or on none (their kernels wait for each other): every rank says whether it could, the communicator adds it up.
+    // (The vote comes before anything is exchanged: the launch-per-iteration loop needs r = 0 on ghost rows.)
+    bool trySlabOnChip(const T* preArg) {
+        if (!allRanksAgree(onChipAllowed() && preArg && sp.lIterations > 0 && !traceEnabled && E->slabOnChipAvailable(sp.lIterations))) return false;
+        (void)takeLease();      // (agreed collectively: this rank launches whether or not another plan of this process holds the chip)
+        exchangeVector(r); exchangeVector(p);      // the kernel reads r_0, p_0 of its halo rows from the ghost rows
+        // A rank whose kernel set refuses after the vote (it should not: the vote covers the communicator's capacity and error state) launches nothing; its
+        // peers' waits then time out, and the verdict below makes every rank redo the step with the streaming loop -- a library does not exit().
+        const bool refused = !E->pcgSolveOnChip(r, p, delta, sp.lIterations, nullptr, nullptr, ctx);
+        if (refused) fprintf(stderr, "Opt(amd): the slab on-chip solve was agreed on but refused by this rank's kernel set; the step will be redone by the streaming loop\n");
+        // all ranks keep their update or none does: the ranks' verdicts (0 fine / 1 a wait timed out) are all-reduced on the device, PCGLinearUpdate checks the sum
+        E->onChipVerdict(scal + 5, refused, ctx);
+        comm.allReduceSum(comm.ctx, scal + 5, 1, (void*)stream);
+        E->onChipApply(delta, scal + 5, refused, ctx);
+        usedOnChip = true; unknownsUpdated = true; return true;
+    }
+    // One GPU: the whole linear solve as one persistent launch with the loop state on chip, if the kernel set has one and the problem fits (iw_onchip.h, sfs_onchip.h,
+    // stencil_onchip.h).  Gauss-Newton (lmc == nullptr): it may end with PCGLinearUpdate (EnergyOps::onChipAppliedUpdate); a traced solve gets its per-iteration
+    // scalars from the kernel.  Levenberg-Marquardt: CtC, the q early-out and the split residual reset happen on chip, the host sees only delta -- and, for a
+    // listening caller (verbosity > 0), the iteration and zeta of the early-out in a pinned word, from which the reference's "breaking at iteration" message is
+    // printed once the step has drained (afterLinearSolve; verbose and silent runs take the SAME path).  Not reproduced there: the message of an early-out decided
+    // after the LAST iteration (its test is dead -- the loop has ended -- and the on-chip kernels do not form it).
+    bool tryOnChip(const T* preArg, const OnChipLm<T>* lmc) {
+        if (!((preArg || E->onChipWithoutPreconditioner()) && onChipAllowed() && sp.lIterations > 0 && takeLease())) return false;
+        double* tr = nullptr;
+        if (traceEnabled) {
+            if (onChipTraceCap < sp.lIterations) { if (onChipTrace) HIP_CHECK(hipFree(onChipTrace)); onChipTraceCap = sp.lIterations; HIP_CHECK(hipMalloc((void**)&onChipTrace, sizeof(double) * 4 * onChipTraceCap)); }
+            tr = onChipTrace;
         }
-        // The whole linear solve as one persistent launch with the loop state on chip, if the kernel set has one and the problem fits (iw_onchip.h);
-        // it ends with PCGLinearUpdate.  A traced solve gets its per-iteration scalars from the kernel (beta numerator by expansion, as below).
-        if (!distributed && (preArg || E->onChipWithoutPreconditioner()) && onChipAllowed() && sp.lIterations > 0 && takeLease()) {
-            double* tr = nullptr;
-            if (traceEnabled) {
-                if (onChipTraceCap < sp.lIterations) { if (onChipTrace) HIP_CHECK(hipFree(onChipTrace)); onChipTraceCap = sp.lIterations; HIP_CHECK(hipMalloc((void**)&onChipTrace, sizeof(double) * 4 * onChipTraceCap)); }
-                tr = onChipTrace;
-            }
-            if (E->pcgSolveOnChip(r, p, delta, sp.lIterations, tr, nullptr, ctx)) {
-                usedOnChip = true; unknownsUpdated = E->onChipAppliedUpdate();
-                if (traceEnabled) {
-                    std::vector<double> h(4 * (size_t)sp.lIterations);
-                    HIP_CHECK(hipMemcpyAsync(h.data(), onChipTrace, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
-                    HIP_CHECK(hipStreamSynchronize(stream));
-                    for (int k = 0; k < sp.lIterations; ++k) {
-                        const double aNum = h[4 * k], aDen = h[4 * k + 1], s2 = h[4 * k + 2], s3 = h[4 * k + 3];
-                        const T al = ((T)aDen > T(0)) ? (T)aNum / (T)aDen : T(0);
-                        const double bNum = std::fmax(aNum - 2.0 * (double)al * s2 + (double)al * (double)al * s3, 0.0);
-                        trace.insert(trace.end(), {(double)sp.nIter, (double)k, aNum, aDen, bNum, 0.0});
-                    }
-                }
-                return true;
-            }
-            dropLease();
+        OnChipLm<T> la = lmc ? *lmc : OnChipLm<T>{};
+        if (lmc) { if (!lmBreak) lmBreak = (double*)allocPinned(64); lmBreak[0] = 0.0; lmBreak[1] = 0.0; la.breakInfo = verbosity > 0 ? lmBreak : nullptr; }
+        if (!E->pcgSolveOnChip(r, p, delta, sp.lIterations, tr, lmc ? &la : nullptr, ctx)) { dropLease(); return false; }
+        usedOnChip = true;
+        if (!lmc) unknownsUpdated = E->onChipAppliedUpdate();
+        if (traceEnabled) {
+            std::vector<double> h(4 * (size_t)sp.lIterations);
+            HIP_CHECK(hipMemcpyAsync(h.data(), onChipTrace, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            for (int k = 0; k < sp.lIterations; ++k) traceRow(k, h[4 * k], h[4 * k + 1], h[4 * k + 2], h[4 * k + 3], false);
         }
+        return true;
+    }
+    // ---- Gauss-Newton PCG loop as one kernel launch per iteration (energy.h PcgIterArgs); returns false if the energy has no such kernel ----
+    bool runLaunchPerIterationGN(const T* preArg) {
         Reduction prev[4] = {redC, Reduction{}, Reduction{}, Reduction{}};   // alphaNum_0 = sum r.p from PCGInit1
         if (distributed) {   // ghost rows of r_0, M and p_0 (written as 0 by evalJTF / PCGInit1_Finish) come from the slab neighbours once
             exchangeVector(r); exchangeVector(p); if (preArg) exchangeVector(preconditioner);
@@ -729,8 +767,8 @@ struct PcgSolver : SolverBase {
             if (distributed && commExt.allReducePlan && lIter + 1 < sp.lIterations && !traceEnabled && E->iterPostsItself(false))
                 planned = commExt.allReducePlan(comm.ctx, 4, &a.post, &nextMail) != 0;
             if (distributed && lIter > 0 && !E->iterStateExchange) exchangeVector(Ap_X);   // kernel with Ap in memory: r and p ghost rows are kept current by the kernel itself
-            if (!distributed && !traceEnabled && trialMode && trialPhase != 2 && nPad * sizeof(T) >= ((size_t)64 << 20) && E->deltaMovable()) { deltaTrial(lIter); a.delta = delta; }
-            if (!E->pcgIteration(a, ctx)) { if (lIter == 0) return false; fprintf(stderr, "pcgIteration refused mid-loop\n"); exit(1); }
+            deltaTrial.beforeLaunch(*this, lIter); a.delta = delta;
+            if (!E->pcgIteration(a, ctx)) { if (lIter == 0) return false; refusedMidLoop(); }
             std::swap(r, r2); std::swap(Ap_X, Ap2); std::swap(p, p2);
             if (distributed && E->iterStateExchange && E->iterExchangeDue) {   // Ap-free kernel: the neighbours' edge rows of r_k and p_k, one grouped exchange
                 std::vector<T*> bases;
@@ -759,14 +797,9 @@ struct PcgSolver : SolverBase {
                     for (int i = 0; i < 4; ++i) { prev[i].partials = tot + i; prev[i].n = 1; }
                 }
             }
-            if (traceEnabled) {
+            if (traceEnabled) {      // (four reads in this order)
                 const double aNum = hostSumLocal(prev[0]), aDen = hostSumLocal(prev[1]), s2 = hostSumLocal(prev[2]), s3 = hostSumLocal(prev[3]);
-                const T al = ((T)aDen > T(0)) ? (T)aNum / (T)aDen : T(0);
-                // an energy that does not precondition starts from p_0 = r_0 / 4 (guardedInvert(1)) but continues with z = r, so the
-                // first alphaNumerator is a quarter of sum r_0^2 -- which is what the expansion needs (see march_pcgIter, stencil_march.h)
-                const double rr = (lIter == 0 && !preArg && !E->usesGraph) ? 4.0 * aNum : aNum;
-                const double bNum = std::fmax(rr - 2.0 * (double)al * s2 + (double)al * (double)al * s3, 0.0);
-                trace.insert(trace.end(), {(double)sp.nIter, (double)lIter, aNum, aDen, bNum, 0.0});
+                traceRow(lIter, aNum, aDen, s2, s3, lIter == 0 && !preArg && !E->usesGraph);
             }
             cur ^= 1;
         }
@@ -776,7 +809,7 @@ struct PcgSolver : SolverBase {
         const T* pLast = E->pcgFinish(p2, delta, ctx);
         if (!pLast) pLast = p;
         finalizeLocal(prev[0], scal + 2);
-        { ScopedKernel k(ctx, "PCGStep2_delta"); k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, delta, pLast, nPacks, scal + 2, nullptr, 0, prev[1].partials, prev[1].n); }
+        step2Delta(pLast, scal + 2, Reduction{}, prev[1]);
         return true;
     }
     // ---- the same for Levenberg-Marquardt (energy.h PcgIterArgs, LM fields).  Launch k applies Step2 and Step3 of iteration k-1 and
@@ -784,20 +817,8 @@ struct PcgSolver : SolverBase {
     // state is exactly the reference's at its break (Step3 runs before fetchQ there too).  Every residual_reset_period-th iteration
     // ends with the reference's split Step2 (delta, A delta, r = b - A delta; :1077-1083) on the generic kernels; the next launch then
     // restarts from that r with beta given directly.  Returns false (nothing touched) if the energy has no such kernel.
-    bool runSingleKernelLoopLM(const T* preArg, T Q0, T q_tolerance) {
-        if (distributed || traceEnabled || keepReferenceP) return false;
-        // The whole LM linear solve as one persistent launch (iw_onchip.h, LMV): CtC, the q early-out and the split residual reset happen on chip, the host
-        // sees only delta -- and, for a listening caller (verbosity > 0), the iteration and zeta of the early-out in a pinned word, from which the reference's "breaking at
-        // iteration" message is printed once the step has drained (round 6: verbose and silent runs take the SAME path).  Not reproduced there: the message of
-        // an early-out decided after the LAST iteration (its test is dead -- the loop has ended -- and the on-chip kernels do not form it).
-        if (onChipAllowed() && (preArg || E->onChipWithoutPreconditioner()) && sp.lIterations > 0 && Q0 == T(0) && takeLease()) {
-            if (!lmBreak) { HIP_CHECK(hipHostMalloc((void**)&lmBreak, 64)); }
-            lmBreak[0] = 0.0; lmBreak[1] = 0.0;
-            OnChipLm<T> la{trust_region_radius, min_lm_diagonal, max_lm_diagonal, q_tolerance, sp.residual_reset_period, CtC};
-            la.breakInfo = verbosity > 0 ? lmBreak : nullptr;
-            if (E->pcgSolveOnChip(r, p, delta, sp.lIterations, nullptr, &la, ctx)) { usedOnChip = true; return true; }
-            dropLease();
-        }
+    bool runLaunchPerIterationLM(const T* preArg) {
+        T Q0 = 0;                                                   // (initLinearSystem: Q_0 is 0)
         if (!delta2) delta2 = allocVec();                       // zero-filled like delta; every launch that updates delta rewrites all of it
         Reduction prev[4] = {redC, Reduction{}, Reduction{}, Reduction{}};
         int cur = 0;
@@ -819,7 +840,7 @@ struct PcgSolver : SolverBase {
             return E->pcgIteration(a, ctx);
         };
         for (int lIter = 0; lIter < sp.lIterations; ++lIter) {
-            if (!issued && !issue(lIter, afterReset)) { if (lIter == 0) return false; fprintf(stderr, "pcgIteration refused mid-loop\n"); exit(1); }
+            if (!issued && !issue(lIter, afterReset)) { if (lIter == 0) return false; refusedMidLoop(); }
             issued = false;
             // adopt launch lIter
             const bool appliedStep2 = lIter > 0 && !issuedRestart;    // it finished iteration lIter-1 (delta, r, z, p) and summed Q_{lIter-1}
@@ -856,17 +877,12 @@ struct PcgSolver : SolverBase {
                 // an early-out) and scratch: if the test below ends the linear solve, their results are simply never adopted (the fetchQ of solver.t:1098
                 // no longer idles the GPU).
                 if (resetNow) { resetKernels(delta2); resetIssued = true; }
-                else if (lIter + 1 < sp.lIterations) { if (!issue(lIter + 1, false)) { fprintf(stderr, "pcgIteration refused mid-loop\n"); exit(1); } issued = true; }
+                else if (lIter + 1 < sp.lIterations) { if (!issue(lIter + 1, false)) refusedMidLoop(); issued = true; }
                 const T Q1 = (T)(tagged ? pollTaggedSum((lIter & 1) ? redQ2 : redQ, tagOf[lIter & 1]) : endHostSum());
                 if (Q1 != Q1) {      // a tagged Q partial never arrived (pollTaggedSum said why): this iteration's test is skipped, Q0 stays the last known value, and the
                     taggedQ = false; //  plan reads Q through the stream (beginHostSum / endHostSum) from here on, so the later early-out tests are real again
                 } else {
-                    const T zeta = T(lIter) * (Q1 - Q0) / Q1;
-                    if (zeta < q_tolerance) {
-                        if (verbosity > 0) printf("zeta=%.18g, breaking at iteration: %d\n", (double)zeta, lIter);
-                        flushOwed(issued ? 1 : 0);
-                        return true;
-                    }
+                    if (qEarlyOut(lIter, Q1, Q0, (T)sp.q_tolerance)) { flushOwed(issued ? 1 : 0); return true; }
                     Q0 = Q1;
                 }
             }
@@ -879,8 +895,7 @@ struct PcgSolver : SolverBase {
                 if (!lastAndSilent) {
                     qDirect = hostSum(redQR);
                     const T Q1 = (T)qDirect;
-                    const T zeta = T(lIter + 1) * (Q1 - Q0) / Q1;
-                    if (zeta < q_tolerance) { if (verbosity > 0) printf("zeta=%.18g, breaking at iteration: %d\n", (double)zeta, lIter + 1); return true; }
+                    if (qEarlyOut(lIter + 1, Q1, Q0, (T)sp.q_tolerance)) return true;
                     Q0 = Q1;
                 }
                 afterReset = true; bNumDirect = redB; bDenDirect = prev[0];
@@ -889,8 +904,7 @@ struct PcgSolver : SolverBase {
         if (deltaOwed) {   // the last iteration's delta += alpha p; its r, z, p and Q are dead (the reference's last fetchQ can only break a finished loop)
             const T *pOwed = nullptr, *aOwed = nullptr;
             (void)E->iterOwedTerm(0, &pOwed, &aOwed);      // (... behind the term a deferring last launch left owed)
-            ScopedKernel k(ctx, "PCGStep2_delta");
-            k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, delta, pNow(), nPacks, nullptr, prev[0].partials, prev[0].n, prev[1].partials, prev[1].n, pOwed, aOwed);
+            step2Delta(pNow(), nullptr, prev[0], prev[1], pOwed, aOwed);
         }
         return true;
     }
@@ -916,9 +930,9 @@ struct PcgSolver : SolverBase {
         }
         exchangeUnknowns();
         E->precompute(ctx);
-        // (inside Opt_ProblemSolve the first step follows at once on the same unknowns: its PCGInit1 rides on this cost pass where the kernel set can -- see stepOnce)
+        // (inside Opt_ProblemSolve the first step follows at once on the same unknowns: its PCGInit1 rides on this cost pass where the kernel set can -- see initLinearSystem)
         jtfReady = false; pendingSteps.clear(); if (chip) chip->setStepSlot(-1);
-        if (!lm && !distributed && insideSolve && E->bindInvariantDuringSolve() && sp.nIterations > 0 && singleKernelAllowed() && r2 && sp.lIterations > 0 &&
+        if (!lm && !distributed && insideSolve && E->bindInvariantDuringSolve() && sp.nIterations > 0 && singleKernelAllowed() && sp.lIterations > 0 &&
             E->evalCostAndJTFInit(redCH, r, p, delta, nPad, redC, ctx)) { jtfReady = true; prevCost = (T)hostSum(redCH); }
         else prevCost = computeCost();
     }
@@ -987,9 +1001,6 @@ struct PcgSolver : SolverBase {
         sp.nIter = f;
     }
     int stepOnce(void** params, bool& again) {
-        const T min_relative_decrease = (T)sp.min_relative_decrease, min_trust_region_radius = (T)sp.min_trust_region_radius;
-        const T max_trust_region_radius = (T)sp.max_trust_region_radius, q_tolerance = (T)sp.q_tolerance, function_tolerance = (T)sp.function_tolerance;
-        T Q0 = 0, Q1 = 0;
         if (!(insideSolve && boundForSolve && E->bindInvariantDuringSolve())) E->bind(params, ctx);      // (EnergyOps::bindInvariantDuringSolve: once per Opt_ProblemSolve where nothing bind() derives can have changed)
         const bool mayDefer = !lm && !distributed && insideSolve && !traceEnabled && E->supportsDeferredSteps();
         if (!pendingSteps.empty() && (!mayDefer || sp.nIter >= sp.nIterations)) {      // (cannot happen: the last step of a solve is never deferred -- kept so that no cost is ever lost)
@@ -1000,91 +1011,85 @@ struct PcgSolver : SolverBase {
         if (sp.nIter >= sp.nIterations) { cleanup(); return 0; }
         const int deferSlot = mayDefer ? (int)pendingSteps.size() : -1;
         if (chip) chip->setStepSlot(deferSlot);
-        bool deferredNow = false;
         const T* preArg = E->usePreconditioner ? preconditioner : nullptr;   // solver.t:467-470: pre = 1 unless the energy preconditions
-
-        // PCGInit1 [+ _Graph + _Finish]: the energy produces r = -J^T F and raw diag(J^T J) (parked in CtC) -- or, for the Gauss-Newton single-kernel loop on
-        // one GPU, r, p = M r, delta = 0 and the partial sums of r.p directly (EnergyOps::evalJTFInit)
+        const Init init = initLinearSystem();
+        solveLinear(preArg, init, false);
+        AfterSolve a = afterLinearSolve(deferSlot);
+        if (a.deferred) {      // (the lease stays with this plan until the steps are settled)
+            pendingSteps.push_back({deferSlot, sp.nIter, usedOnChip});
+            usedOnChip = false;
+            sp.nIter += 1;
+            onChipCleanStep();
+            return 1;
+        }
+        if (!settleAndRedo(preArg, deferSlot, a, again)) return 1;
+        if (lm && !lmDecision(a.newCost, a.modelCostChange)) return 0;
+        if (!lm) { if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)a.newCost); prevCost = a.newCost; }
+        sp.nIter += 1;
+        onChipCleanStep();
+        return 1;
+    }
+    // PCGInit1 [+ _Graph + _Finish]: the energy produces r = -J^T F and raw diag(J^T J) (parked in CtC) -- or, for the Gauss-Newton single-kernel loop on one GPU,
+    // r, p = M r, delta = 0 and the partial sums of r.p directly (EnergyOps::evalJTFInit), or for LM on one GPU all that PCGFinalizeDiagonal does too (evalJTFInitLM).
+    // LM's fetchQ behind it (solver.t:1050) is not performed: Q_0 = 1/2 sum delta . (r + b) with the delta PCGInit1 has just zeroed is exactly 0 for every finite r.
+    enum class Init { carried, jtfInit, jtfInitLM, generic };      // carried: the previous step's cost pass ran this PCGInit1 (EnergyOps::evalCostAndJTFInit)
+    Init initLinearSystem() {
         unknownsUpdated = false;
-        const bool jtfCarried = jtfReady && insideSolve;      // r, p and the partial sums of r.p are already there: the previous step's cost pass wrote them from these very unknowns
+        aSlot = 0;
+        const bool carried = jtfReady && insideSolve;      // r, p and the partial sums of r.p are already there: the previous step's cost pass wrote them from these very unknowns
         jtfReady = false;
-        const bool fusedInit = !lm && !distributed && singleKernelAllowed() && r2 && sp.lIterations > 0 && (jtfCarried || E->evalJTFInit(r, p, delta, nPad, redC, ctx));
-        bool fusedInitLM = false;
+        if (!lm && !distributed && singleKernelAllowed() && sp.lIterations > 0 && (carried || E->evalJTFInit(r, p, delta, nPad, redC, ctx)))
+            return carried ? Init::carried : Init::jtfInit;
         if (lm && !distributed) {
             LmInitArgs<T> la{CtC, SSq, r, delta, preconditioner, b, p, trust_region_radius, min_lm_diagonal, max_lm_diagonal, sp.nIter == 0 ? 1 : 0, &redC, &redQ};
-            fusedInitLM = E->evalJTFInitLM(la, ctx);
+            if (E->evalJTFInitLM(la, ctx)) return Init::jtfInitLM;
         }
-        if (!fusedInit && !fusedInitLM) E->evalJTF(r, CtC, ctx);
-        if (!lm && !fusedInit) {
-            ScopedKernel k(ctx, "PCGInit1_Finish");
-            k_initFinish<T><<<streamGrid, kBlock, 0, stream>>>(r, CtC, preconditioner, p, delta, nPacks, E->usePreconditioner ? 1 : 0, E->usesGraph ? 1 : 0, redC.partials);
-            redC.n = streamGrid;
-        }
-        aSlot = 0;
-        if (lm) {
-            if (!fusedInitLM) {   // PCGInit1_Finish + (first outer iteration) PCGSaveSSq + PCGFinalizeDiagonal in one pass
-                ScopedKernel k(ctx, "PCGFinalizeDiagonal");
-                k_finalizeDiagonal<T, true><<<streamGrid, kBlock, 0, stream>>>(CtC, SSq, r, delta, preconditioner, b, p, nPacks, trust_region_radius, min_lm_diagonal,
-                                                                               max_lm_diagonal, redC.partials, redQ.partials, E->usePreconditioner ? 1 : 0,
-                                                                               E->usesGraph ? 1 : 0, sp.nIter == 0 ? 1 : 0);
-                redC.n = streamGrid; redQ.n = streamGrid;
+        E->evalJTF(r, CtC, ctx);
+        if (!lm) { initFinish(); return Init::generic; }
+        ScopedKernel k(ctx, "PCGFinalizeDiagonal");      // PCGInit1_Finish + (first outer iteration) PCGSaveSSq + PCGFinalizeDiagonal in one pass
+        k_finalizeDiagonal<T, true><<<streamGrid, kBlock, 0, stream>>>(CtC, SSq, r, delta, preconditioner, b, p, nPacks, trust_region_radius, min_lm_diagonal,
+                                                                       max_lm_diagonal, redC.partials, redQ.partials, E->usePreconditioner ? 1 : 0,
+                                                                       E->usesGraph ? 1 : 0, sp.nIter == 0 ? 1 : 0);
+        redC.n = streamGrid; redQ.n = streamGrid;
+        return Init::generic;
+    }
+    // The one place that picks the linear solve's path, the first that takes it: (1) on chip -- in slab mode behind the vote every rank issues --, (2) the kernel set's
+    // launch-per-iteration loop, (3) the reference-order loop.  (1) and (2) need singleKernelAllowed() (off with OPT_AMD_ONEKERNEL=0 or amd_reference_order=1), in LM
+    // also OPT_AMD_ONEKERNEL_LM, one GPU and no trace.  A redo after an on-chip time-out stops short of (3): false, and the step runs again from its PCGInit1.
+    bool solveLinear(const T* preArg, Init init, bool redo) {
+        if (singleKernelAllowed()) {
+            if (lm) {
+                const OnChipLm<T> la{trust_region_radius, min_lm_diagonal, max_lm_diagonal, (T)sp.q_tolerance, sp.residual_reset_period, CtC};
+                if (oneKernelLM && !distributed && !traceEnabled && (tryOnChip(preArg, &la) || runLaunchPerIterationLM(preArg))) return true;
+            } else {
+                if (distributed ? trySlabOnChip(preArg) : tryOnChip(preArg, nullptr)) return true;
+                if ((!distributed || E->slabIterationAvailable()) && runLaunchPerIterationGN(preArg)) return true;
             }
-            preArg = E->usePreconditioner ? preconditioner : nullptr;
-            // fetchQ, solver.t:1050: Q_0 = 1/2 sum delta . (r + b) with the delta PCGInit1 has just zeroed -- exactly 0 for every finite r, so the
-            // blocking read (one full drain of the stream per outer iteration) is not performed
-            Q0 = T(0);
         }
-
-        // Loop structure: the reference runs Step1, Step2, Step3 per iteration (:1056-1103).  Here Step3 of
-        // iteration k is fused into Step1 of iteration k+1 when the energy offers that kernel (it only
-        // feeds the next Step1; after the last iteration p is dead).
-        bool pendingStep3 = false;
-        Reduction bNum;
-        const bool single = singleKernelAllowed() && r2 && (lm ? (oneKernelLM && runSingleKernelLoopLM(preArg, Q0, q_tolerance)) : runSingleKernelLoop(preArg));
-        if (fusedInit && !single) {      // the kernel set accepted evalJTFInit but refused the loop (it should not): PCGInit1 again for the generic loop -- a library does not exit()
+        if (redo) return false;
+        if (init == Init::carried || init == Init::jtfInit) {      // the kernel set accepted evalJTFInit but refused the loop (it should not): PCGInit1 again -- a library does not exit()
             fprintf(stderr, "Opt(amd): the kernel set accepted evalJTFInit but refused the single-kernel loop; this step runs on the generic kernels\n");
             E->evalJTF(r, CtC, ctx);
-            ScopedKernel k(ctx, "PCGInit1_Finish");
-            k_initFinish<T><<<streamGrid, kBlock, 0, stream>>>(r, CtC, preconditioner, p, delta, nPacks, E->usePreconditioner ? 1 : 0, E->usesGraph ? 1 : 0, redC.partials);
-            redC.n = streamGrid;
+            initFinish();
         }
-        if (!single) finalizeTo(redC, scal + aSlot);   // alphaNumerator = sum r.p as one device scalar (the single-kernel loops sum the partials in their first launch)
-        // Step3 of the previous iteration (when pending) and Step1 of the next one.  None of it touches what survives a q early-out
-        // (delta, and p only through the very Step3 the reference also runs before its q test), so in LM it is enqueued BEFORE the
-        // host reads q of the current iteration: the blocking fetchQ of solver.t:1098 then overlaps with useful kernels instead of
-        // draining the GPU once per PCG iteration.  With tracing on, the original order (decide, then launch) is kept.
-        Reduction aDen;
-        auto stepThreeAndOne = [&]() {
-            bool applied = false;
-            if (pendingStep3) {
-                exchangeVector(z);      // (an energy without the fused kernel refuses: the generic PCGStep3 below)
-                applied = E->applyJTJFused(p, z, p2, Ap_X, lm ? CtC : nullptr, &redA, bNum, scal + aSlot, scal + (aSlot ^ 1), ctx);
-                if (applied) std::swap(p, p2);
-                if (!applied) {
-                    ScopedKernel k(ctx, "PCGStep3");
-                    k_step3<T><<<streamGrid, kBlock, 0, stream>>>(z, p, nPacks, bNum.partials, bNum.n, scal + aSlot, scal + (aSlot ^ 1));
-                }
-                aSlot ^= 1;   // alphaNumerator <- betaNumerator (solver.t:1091)
-                pendingStep3 = false;
-            }
-            if (!applied) {
-                exchangeVector(p);
-                E->applyJTJ(p, Ap_X, lm ? CtC : nullptr, &redA, ctx);    // PCGStep1 (+_Graph)
-            }
-            aDen = forConsumers(redA, 0);
-        };
+        runReferenceOrderLoop(preArg);
+        return true;
+    }
+    // The reference's loop: PCGStep1, PCGStep2, PCGStep3 per iteration (solver.t:1056-1103).  Step3 of iteration k is fused into Step1 of iteration k+1 when the energy
+    // offers that kernel (it only feeds the next Step1; after the last iteration p is dead).  None of Step3 + Step1 touches what survives a q early-out (delta, and p only
+    // through the very Step3 the reference also runs before its q test), so in LM it is enqueued BEFORE the host reads q of the current iteration: the blocking fetchQ of
+    // solver.t:1098 then overlaps with useful kernels instead of draining the GPU once per PCG iteration.  With tracing on, the original order (decide, then launch) is kept.
+    void runReferenceOrderLoop(const T* preArg) {
+        finalizeTo(redC, scal + aSlot);   // alphaNumerator = sum r.p as one device scalar (the single-kernel loops sum the partials in their first launch)
         const bool speculate = !traceEnabled;
-        if (!single && sp.lIterations > 0) stepThreeAndOne();     // Step1 of iteration 0
-        for (int lIter = 0; !single && lIter < sp.lIterations; ++lIter) {
+        T Q0 = 0;                         // (initLinearSystem: Q_0 is 0)
+        Reduction aDen, bNum;
+        if (sp.lIterations > 0) aDen = stepThreeAndOne(nullptr);     // Step1 of iteration 0
+        for (int lIter = 0; lIter < sp.lIterations; ++lIter) {
             const bool reset = lm && sp.residual_reset_period > 0 && ((lIter + 1) % sp.residual_reset_period) == 0;
             // After the last iteration only delta survives: r, z, the beta numerator and (unless someone listens for the "breaking" message) Q are dead, so the
             // last PCGStep2 -- or the last split residual reset -- shrinks to its delta += alpha p.
-            const bool deltaOnly = lIter + 1 >= sp.lIterations && !traceEnabled && !keepReferenceP && (!lm || verbosity == 0);
-            if (deltaOnly) {
-                ScopedKernel k(ctx, "PCGStep2_delta");
-                k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, delta, p, nPacks, scal + aSlot, nullptr, 0, aDen.partials, aDen.n);
-                break;
-            }
+            if (lIter + 1 >= sp.lIterations && !traceEnabled && (!lm || verbosity == 0)) { step2Delta(p, scal + aSlot, Reduction{}, aDen); break; }
             if (reset) {   // solver.t:1077-1083
                 { ScopedKernel k(ctx, "PCGStep2_1stHalf"); k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, delta, p, nPacks, scal + aSlot, nullptr, 0, aDen.partials, aDen.n); }
                 exchangeVector(delta);
@@ -1098,91 +1103,87 @@ struct PcgSolver : SolverBase {
                 else k_step2<T, false><<<streamGrid, kBlock, 0, stream>>>(delta, p, r, Ap_X, preArg, nullptr, z, nPacks, scal + aSlot, aDen.partials, aDen.n, redB.partials, nullptr);
                 redB.n = streamGrid; redQ.n = streamGrid;
             }
-            bNum = forConsumers(redB, 1);
-            pendingStep3 = true;   // PCGStep3 of this iteration runs with the next PCGStep1
+            bNum = forConsumers(redB, 1);      // (PCGStep3 of this iteration runs with the next PCGStep1)
             const bool more = lIter + 1 < sp.lIterations;
             double qh = 0;
             const bool deadFetch = lm && !more && verbosity == 0 && !traceEnabled;   // fetchQ after the last iteration only feeds the "breaking" message
             if (deadFetch) {
             } else if (lm && speculate) {
                 beginHostSum(redQ);
-                if (more) stepThreeAndOne();
+                if (more) aDen = stepThreeAndOne(&bNum);
                 qh = endHostSum();
             } else {
                 if (lm) qh = hostSum(redQ);
                 if (traceEnabled) record(lIter, aDen, bNum, qh);
             }
             if (lm && !deadFetch) {   // solver.t:1093-1102
-                Q1 = (T)qh;
-                T zeta = T(lIter + 1) * (Q1 - Q0) / Q1;
-                if (zeta < q_tolerance) { if (verbosity > 0) printf("zeta=%.18g, breaking at iteration: %d\n", (double)zeta, lIter + 1); break; }
+                const T Q1 = (T)qh;
+                if (qEarlyOut(lIter + 1, Q1, Q0, (T)sp.q_tolerance)) break;
                 Q0 = Q1;
             }
-            if (more && !(lm && speculate)) stepThreeAndOne();
+            if (more && !(lm && speculate)) aDen = stepThreeAndOne(&bNum);
         }
-        if (pendingStep3 && keepReferenceP) {   // the reference's final PCGStep3 only matters to someone probing `p`
-            ScopedKernel k(ctx, "PCGStep3");
-            k_step3<T><<<streamGrid, kBlock, 0, stream>>>(z, p, nPacks, bNum.partials, bNum.n, scal + aSlot, scal + (aSlot ^ 1));
-            aSlot ^= 1;
+    }
+    // PCGStep3 of the previous iteration (bNum: its beta numerator; nullptr before iteration 0) and PCGStep1 of the next one, as one kernel where the energy fuses them.
+    // Returns the alpha denominator as its consumers read it.
+    Reduction stepThreeAndOne(const Reduction* bNum) {
+        bool applied = false;
+        if (bNum) {
+            exchangeVector(z);      // (an energy without the fused kernel refuses: the generic PCGStep3 below)
+            applied = E->applyJTJFused(p, z, p2, Ap_X, lm ? CtC : nullptr, &redA, *bNum, scal + aSlot, scal + (aSlot ^ 1), ctx);
+            if (applied) std::swap(p, p2);
+            else { ScopedKernel k(ctx, "PCGStep3"); k_step3<T><<<streamGrid, kBlock, 0, stream>>>(z, p, nPacks, bNum->partials, bNum->n, scal + aSlot, scal + (aSlot ^ 1)); }
+            aSlot ^= 1;   // alphaNumerator <- betaNumerator (solver.t:1091)
         }
-
-        T model_cost_change = 0;
-        T newCost = 0;
-        // What follows the linear solve (solver.t:1108-1117): model cost, savePreviousUnknowns + PCGLinearUpdate, precompute, the new cost.  The reference reads the
-        // model cost, then updates, then reads the new cost (two blocking copies); neither value steers anything before both are known, so all of it is enqueued
-        // and the stream is drained once.
-        auto afterLinearSolve = [&]() {
-            if (lm) {   // solver.t:1108-1113, 819-827
-                exchangeVector(delta);
-                E->evalModelCost(delta, distributed ? redA : redMH, ctx);   // (its own partials buffer: the value is read together with the new cost below)
-                imageOp(3);   // savePreviousUnknowns + PCGLinearUpdate
-            } else if (!unknownsUpdated) {   // PCGLinearUpdate (behind an on-chip solve that left the update to the solver: guarded by the launch's failure word where the kernel set can)
-                if (!(usedOnChip && E->onChipGuardedUpdate(delta, ctx))) imageOp(0);
-            }
-            exchangeUnknowns();
-            E->precompute(ctx);
-            if (lm && !distributed) {
-                E->evalCost(redCH, ctx);                   // both sets of partials are written straight to pinned memory: one drain, no copy kernels
-                drain();
-                if (usedOnChip && verbosity > 0 && lmBreak && lmBreak[0] > 0.0 && !chip->failedPeek()) { printf("zeta=%.18g, breaking at iteration: %d\n", lmBreak[1], (int)lmBreak[0] - 1); lmBreak[0] = 0.0; }
-                double sm = 0, sc = 0;
-                for (int i = 0; i < redMH.n; ++i) sm += redMH.partials[i];
-                for (int i = 0; i < redCH.n; ++i) sc += redCH.partials[i];
-                newCost = (T)sc;
-                const T model_cost = (T)sm;
-                if (verbosity > 0) printf(" cost=%f \n model_cost=%f \n", (double)prevCost, (double)model_cost);
-                model_cost_change = prevCost - model_cost;
-                if (verbosity > 0) printf(" model_cost_change=%f \n", (double)model_cost_change);
-            } else {
-                if (lm) {
-                    T model_cost = (T)hostSum(redA);
-                    if (verbosity > 0) printf(" cost=%f \n model_cost=%f \n", (double)prevCost, (double)model_cost);
-                    model_cost_change = prevCost - model_cost;
-                    if (verbosity > 0) printf(" model_cost_change=%f \n", (double)model_cost_change);
-                }
-                // Gauss-Newton inside Opt_ProblemSolve with another step to come: that step's PCGInit1 reads the unknowns this cost reads, and no caller code runs in
-                // between -- one pass does both where the kernel set can (same cost bits: same grid, same expressions).  A step on the generic kernels (back-off after
-                // an on-chip time-out included) does not ask.
-                const bool carry = !lm && !distributed && insideSolve && boundForSolve && E->bindInvariantDuringSolve() && sp.nIter + 1 < sp.nIterations &&
-                                   singleKernelAllowed() && r2 && sp.lIterations > 0;
-                Reduction& costR = deferSlot >= 0 ? costRing[deferSlot] : redCH;
-                if (deferSlot >= 0 && !costR.partials) { HIP_CHECK(hipHostMalloc((void**)&costR.partials, 2 * kMaxPartials * sizeof(double))); costR.hostVisible = true; }
-                if (carry && E->evalCostAndJTFInit(costR, r, p, delta, nPad, redC, ctx)) {
-                    jtfReady = true;
-                    if (deferSlot >= 0 && deferSlot + 1 < kDefer) deferredNow = true;      // nothing is read back now: the next step is enqueued behind this one
-                    else newCost = (T)hostSum(costR);
-                } else newCost = computeCost();
-            }
-        };
-        afterLinearSolve();
-
-        if (deferredNow) {      // (the lease stays with this plan until the steps are settled)
-            pendingSteps.push_back({deferSlot, sp.nIter, usedOnChip});
-            usedOnChip = false;
-            sp.nIter += 1;
-            onChipCleanStep();
-            return 1;
+        if (!applied) {
+            exchangeVector(p);
+            E->applyJTJ(p, Ap_X, lm ? CtC : nullptr, &redA, ctx);    // PCGStep1 (+_Graph)
         }
+        return forConsumers(redA, 0);
+    }
+    // What follows the linear solve (solver.t:1108-1117): model cost, savePreviousUnknowns + PCGLinearUpdate, precompute, the new cost.  The reference reads the
+    // model cost, then updates, then reads the new cost (two blocking copies); neither value steers anything before both are known, so all of it is enqueued
+    // and the stream is drained once.  deferred: nothing was read back (deferSlot: this step's cost buffer, or -1).
+    struct AfterSolve { T newCost = 0, modelCostChange = 0; bool deferred = false; };
+    AfterSolve afterLinearSolve(int deferSlot) {
+        AfterSolve a;
+        if (lm) {   // solver.t:1108-1113, 819-827
+            exchangeVector(delta);
+            E->evalModelCost(delta, distributed ? redA : redMH, ctx);   // (its own partials buffer: the value is read together with the new cost below)
+            imageOp(3);   // savePreviousUnknowns + PCGLinearUpdate
+        } else if (!unknownsUpdated) {   // PCGLinearUpdate (behind an on-chip solve that left the update to the solver: guarded by the launch's failure word where the kernel set can)
+            if (!(usedOnChip && E->onChipGuardedUpdate(delta, ctx))) imageOp(0);
+        }
+        exchangeUnknowns();
+        E->precompute(ctx);
+        if (lm && !distributed) {
+            E->evalCost(redCH, ctx);                   // both sets of partials are written straight to pinned memory: one drain, no copy kernels
+            drain();
+            if (usedOnChip && verbosity > 0 && lmBreak && lmBreak[0] > 0.0 && !chip->failedPeek()) { printf("zeta=%.18g, breaking at iteration: %d\n", lmBreak[1], (int)lmBreak[0] - 1); lmBreak[0] = 0.0; }
+            double sm = 0, sc = 0;
+            for (int i = 0; i < redMH.n; ++i) sm += redMH.partials[i];
+            for (int i = 0; i < redCH.n; ++i) sc += redCH.partials[i];
+            a.newCost = (T)sc;
+            a.modelCostChange = modelCostChange((T)sm);
+            return a;
+        }
+        if (lm) a.modelCostChange = modelCostChange((T)hostSum(redA));
+        // Gauss-Newton inside Opt_ProblemSolve with another step to come: that step's PCGInit1 reads the unknowns this cost reads, and no caller code runs in
+        // between -- one pass does both where the kernel set can (same cost bits: same grid, same expressions).  A step on the generic kernels (back-off after
+        // an on-chip time-out included) does not ask.
+        const bool carry = !lm && !distributed && insideSolve && boundForSolve && E->bindInvariantDuringSolve() && sp.nIter + 1 < sp.nIterations &&
+                           singleKernelAllowed() && sp.lIterations > 0;
+        Reduction& costR = deferSlot >= 0 ? costRing[deferSlot] : redCH;
+        if (deferSlot >= 0 && !costR.partials) { costR.partials = (double*)allocPinned(2 * kMaxPartials * sizeof(double)); costR.hostVisible = true; }
+        if (carry && E->evalCostAndJTFInit(costR, r, p, delta, nPad, redC, ctx)) {
+            jtfReady = true;
+            if (deferSlot >= 0 && deferSlot + 1 < kDefer) a.deferred = true;      // nothing is read back now: the next step is enqueued behind this one
+            else a.newCost = (T)hostSum(costR);
+        } else a.newCost = computeCost();
+        return a;
+    }
+    // Behind the cost read: the deferred steps, then this step's on-chip verdict (a time-out redoes the linear solve).  false: the step ends here.
+    bool settleAndRedo(const T* preArg, int deferSlot, AfterSolve& a, bool& again) {
         if (!pendingSteps.empty()) {      // the stream has drained (this step's cost was read): what the deferred steps before it left
             const bool thisOnChip = usedOnChip;
             const int f = settlePending();
@@ -1190,70 +1191,62 @@ struct PcgSolver : SolverBase {
                 // from step f on nothing was applied -- unless THIS step ran on the streaming kernels (it cannot while the path is armed; if it did, it was a valid step from
                 // the unknowns of step f and counts as that step)
                 rewindTo(f);
-                if (!thisOnChip) { if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)newCost); prevCost = newCost; sp.nIter = f + 1; }
-                return 1;      // (jtfReady says whether this step's cost pass carried a PCGInit1 for the unknowns as they stand; the last step of a solve carries none)
+                if (!thisOnChip) { if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)a.newCost); prevCost = a.newCost; sp.nIter = f + 1; }
+                return false;      // (jtfReady says whether this step's cost pass carried a PCGInit1 for the unknowns as they stand; the last step of a solve carries none)
             }
             if (!usedOnChip) dropLease();
         }
         lastStepOnChip = usedOnChip;
-        if (usedOnChip) {      // (the stream has drained: the cost was read)
-            usedOnChip = false;
-            if (!chip->failedNow()) dropLease();      // the launch has left the chip
-            else {
-                onChipFailure("this linear solve is redone");
-                unknownsUpdated = false;
-                if (lm) {      // the kernel produced no delta: the update above added nothing meaningful -- back to the saved unknowns, then the launch-per-iteration loop
-                    imageOp(2);
-                    E->precompute(ctx);      // (workgroups that had finished before the others gave up may have written their delta: the update above was then not the identity)
-                    HIP_CHECK(hipMemsetAsync(delta, 0, nPad * sizeof(T), stream));
-                    // an energy whose LM loop is the generic one (no single-kernel LM iteration): the whole step again, from its PCGInit1, on the generic kernels
-                    if (!runSingleKernelLoopLM(preArg, T(0), q_tolerance)) { again = true; return 1; }
-                } else {
-                    // Gauss-Newton: nothing was applied (iw_applyDelta checks the flag -- in slab mode the all-reduced verdict, so no rank kept its update).
-                    // The redone loop starts from delta = 0 as PCGInit1 left it: the ROWS = 16 variant accumulates delta in memory while it runs.
-                    HIP_CHECK(hipMemsetAsync(delta, 0, nPad * sizeof(T), stream));
-                    if (!runSingleKernelLoop(preArg)) { again = true; return 1; }      // (no single-kernel loop either: the whole step again on the generic kernels)
-                }
-                afterLinearSolve();
-            }
+        if (!usedOnChip) return true;      // (the stream has drained: the cost was read)
+        usedOnChip = false;
+        if (!chip->failedNow()) { dropLease(); return true; }      // the launch has left the chip
+        onChipFailure("this linear solve is redone");
+        unknownsUpdated = false;
+        if (lm) {      // the kernel produced no delta: the update above added nothing meaningful -- back to the saved unknowns, then the launch-per-iteration loop
+            imageOp(2);
+            E->precompute(ctx);      // (workgroups that had finished before the others gave up may have written their delta: the update above was then not the identity)
         }
-        if (lm) {   // solver.t:1119-1157
-            T cost_change = prevCost - newCost;
-            T relative_decrease = cost_change / model_cost_change;
-            if (cost_change >= 0 && relative_decrease > min_relative_decrease) {
-                T absolute_function_tolerance = prevCost * function_tolerance;
-                if (cost_change <= absolute_function_tolerance) {
-                    if (verbosity > 0) printf("\nFunction tolerance reached, exiting\n");
-                    cleanup(); return 0;
-                }
-                // Terra promotes these literals to double; results are stored back as opt_float (solver.t:1135-1139)
-                double step_quality = (double)relative_decrease, min_factor = 1.0 / 3.0;
-                double tmp_factor = 1.0 - std::pow(2.0 * step_quality - 1.0, 3.0);
-                trust_region_radius = (T)((double)trust_region_radius / std::fmax(min_factor, tmp_factor));
-                trust_region_radius = std::fmin(trust_region_radius, max_trust_region_radius);
-                radius_decrease_factor = T(2.0);
-                prevCost = newCost;
-            } else {
-                imageOp(2);   // revertUpdate
-                trust_region_radius = trust_region_radius / radius_decrease_factor;
-                if (verbosity > 0) printf(" trust_region_radius=%f \n", (double)trust_region_radius);
-                radius_decrease_factor = T(2.0) * radius_decrease_factor;
-                if (trust_region_radius <= min_trust_region_radius) {
-                    if (verbosity > 0) printf("\nTrust_region_radius is less than the min, exiting\n");
-                    cleanup(); return 0;
-                }
-                if (verbosity > 0) printf("REVERT\n");
-                exchangeUnknowns();
-                E->precompute(ctx);
-                HIP_CHECK(hipStreamSynchronize(stream));   // results visible when the call returns
+        // Gauss-Newton: nothing was applied (iw_applyDelta checks the flag -- in slab mode the all-reduced verdict, so no rank kept its update).
+        // The redone loop starts from delta = 0 as PCGInit1 left it: the ROWS = 16 variant accumulates delta in memory while it runs.
+        HIP_CHECK(hipMemsetAsync(delta, 0, nPad * sizeof(T), stream));
+        if (!solveLinear(preArg, Init::generic, true)) { again = true; return false; }      // (no launch-per-iteration loop: the whole step again on the generic kernels)
+        a = afterLinearSolve(deferSlot);
+        return true;
+    }
+    // LM's accept / reject (solver.t:1119-1157).  false: a tolerance was reached and the solve has ended (cleanup has run).
+    bool lmDecision(T newCost, T model_cost_change) {
+        const T min_relative_decrease = (T)sp.min_relative_decrease, min_trust_region_radius = (T)sp.min_trust_region_radius;
+        const T max_trust_region_radius = (T)sp.max_trust_region_radius, function_tolerance = (T)sp.function_tolerance;
+        T cost_change = prevCost - newCost;
+        T relative_decrease = cost_change / model_cost_change;
+        if (cost_change >= 0 && relative_decrease > min_relative_decrease) {
+            T absolute_function_tolerance = prevCost * function_tolerance;
+            if (cost_change <= absolute_function_tolerance) {
+                if (verbosity > 0) printf("\nFunction tolerance reached, exiting\n");
+                cleanup(); return false;
             }
-        } else {
-            if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)newCost);
+            // Terra promotes these literals to double; results are stored back as opt_float (solver.t:1135-1139)
+            double step_quality = (double)relative_decrease, min_factor = 1.0 / 3.0;
+            double tmp_factor = 1.0 - std::pow(2.0 * step_quality - 1.0, 3.0);
+            trust_region_radius = (T)((double)trust_region_radius / std::fmax(min_factor, tmp_factor));
+            trust_region_radius = std::fmin(trust_region_radius, max_trust_region_radius);
+            radius_decrease_factor = T(2.0);
             prevCost = newCost;
+        } else {
+            imageOp(2);   // revertUpdate
+            trust_region_radius = trust_region_radius / radius_decrease_factor;
+            if (verbosity > 0) printf(" trust_region_radius=%f \n", (double)trust_region_radius);
+            radius_decrease_factor = T(2.0) * radius_decrease_factor;
+            if (trust_region_radius <= min_trust_region_radius) {
+                if (verbosity > 0) printf("\nTrust_region_radius is less than the min, exiting\n");
+                cleanup(); return false;
+            }
+            if (verbosity > 0) printf("REVERT\n");
+            exchangeUnknowns();
+            E->precompute(ctx);
+            HIP_CHECK(hipStreamSynchronize(stream));   // results visible when the call returns
         }
-        sp.nIter += 1;
-        onChipCleanStep();
-        return 1;
+        return true;
     }
 
     double cost() const override { return (double)prevCost; }   // solver.t:1179-1182
@@ -1274,8 +1267,7 @@ struct PcgSolver : SolverBase {
         if (onChipFailures) d += "; onchip_fallbacks=" + std::to_string(onChipFailures) + "; onchip_backoff_steps_left=" + std::to_string(onChipOff() ? onChipBackoff - onChipCleanSteps : 0);
         // what Opt_ProblemSolve does beyond Init + Step by Step on this plan, and where the trial over delta's placement stands
         if (!lm && !distributed && E->supportsDeferredSteps()) d += "; solve_enqueues_steps_back_to_back=up to " + std::to_string(kDefer - 1);
-        if (!lm && !distributed && E->deltaMovable() && nPad * sizeof(T) >= ((size_t)64 << 20))
-            d += std::string("; delta_placement_trial=") + (!trialMode ? "off" : trialPhase == 2 ? "done" : trialPhase == 1 ? "running" : "before the first linear solve of more than 28 launches");
+        d += deltaTrial.describe(*this);
         d += std::string("; solver=") + (lm ? "LM" : "GN") + "; distributed=" + (distributed ? "yes" : "no") + "; comm_world=" + std::to_string(distributed ? comm.world : 1) +
              "; comm_ext=" + (commExt.onChipPlan ? "onChipPlan " : "") + (commExt.allReducePost ? "allReducePost " : "") + (commExt.allReducePartials ? "allReducePartials" : "");
         return d;

@@ -228,7 +228,7 @@ def test_config4_arap_500k_lm_steps_vs_oracle(oracle_lib):
 def test_delta_placement_trial_changes_no_bit(monkeypatch, capfd):
     """Round 6: delta is the one vector the Gauss-Newton loop reads and writes, and the time of a launch follows the region the allocator put it in (profiles/NOTES.md).  The
     first long linear solve of a large single-GPU plan copies delta into a fresh vector every six launches (four candidates, each window timed) and goes on in the fastest
-    (PcgSolver::deltaTrial).  A copy is a copy: unknowns and costs are the bits of a run with the trial switched off; the trial does run (its report names four timings) and a
+    (PcgSolver::DeltaTrial).  A copy is a copy: unknowns and costs are the bits of a run with the trial switched off; the trial does run (its report names four timings) and a
     second solve on the same plan does not repeat it; a solve too short for four windows leaves everything as it is."""
     P = wl.image_warping(2400, 2400, random_state=6, perturb=0.3)
     res = []

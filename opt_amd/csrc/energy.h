@@ -29,6 +29,27 @@ struct UnknownImage {
     long offset;      // first scalar of this image in the solver's unknown vector
 };
 
+// What one EnergyOps::pcgIteration launch did beyond writing the vectors and sums it was given (PcgIterArgs::result).  The defaults are those of a kernel set
+// that keeps the loop state in the caller's buffers and updates delta in every launch.
+template <class T>
+struct PcgIterResult {
+    bool exchangeDue = true;            // slab mode, IterTraits::stateExchange: the neighbours must refresh the ghost rows of the loop state after this launch (deep ghost zones let a kernel skip some)
+    int nExchange = 0;                  // ... of these vectors (solver layout); 0: of the rNew / pNew the launch was given
+    T* exchange[2] = {nullptr, nullptr};
+    const T* p = nullptr;               // where this launch's search direction lives if the kernel set keeps the directions in buffers of its own (nullptr: in pNew)
+    bool wroteDelta = true;             // LM loop: the launch wrote deltaOut (a kernel set that pairs its delta updates writes it every second launch) ...
+    const T *owedP = nullptr, *owedAlpha = nullptr;      // ... and the term owedAlpha[0] * owedP a deferring launch left owed to delta (EnergyOps::addOwedTerm, or a solver kernel that adds it in its own pass)
+};
+
+// What holds for every launch of a launch-per-iteration loop (EnergyOps::iterTraits, asked before the loop).
+struct IterTraits {
+    bool stateExchange = false;         // slab mode: the solver exchanges the ghost rows of the loop state after a launch (PcgIterResult::exchangeDue; else those of Ap before it)
+    bool takesMail = false;             // the kernels can read the previous launch's sums from a posted all-reduce (PcgIterArgs::mail)
+    bool postsItself = false;           // ... and carry out a planned post themselves (PcgIterArgs::post)
+    bool slabAvailable = true;          // slab mode: pcgIteration will accept the launches (the solver refreshes the ghost rows of r_0, p_0 and M for that loop only: the
+                                        // three-kernel loop relies on r being 0 on ghost rows -- its flat sums run over them)
+};
+
 // Arguments of the single-kernel PCG iteration (EnergyOps::pcgIteration).  The reference runs three kernels per
 // iteration -- PCGStep1 (Ap = A p, alphaDen = p.Ap), PCGStep2 (delta += alpha p, r -= alpha Ap, z = M r,
 // betaNum = z.r), PCGStep3 (p = z + beta p) -- separated by two grid-wide sums (solverGPUGaussNewton.t:1056-1091).
@@ -67,6 +88,7 @@ struct PcgIterArgs {
     OptAmd_MailPost post = {};
     T* deltaOut = nullptr;                               // if set, the updated delta goes here instead of in place (lets the solver enqueue
                                                          // the next launch before it has read Q: an early-out then still finds the old delta)
+    PcgIterResult<T>* result = nullptr;                  // set by the solver; a kernel set whose launches differ from the defaults says so here
 };
 
 // Arguments of EnergyOps::evalJTFInitLM: what PCGInit1 + PCGSaveSSq + PCGFinalizeDiagonal (solver.t:361-419, 624-664; solver.hip k_finalizeDiagonal<T, true>) read and write.
@@ -99,11 +121,8 @@ struct EnergyOps {
     bool usePreconditioner = false;   // reference o.t:214 default
     bool usesGraph = false;
     Slab slab;
-    bool iterStateExchange = false;   // set by pcgIteration: in slab mode the solver exchanges the ghost rows of r and p after a launch (else of Ap before it)
-    bool iterExchangeDue = true;      // ... and whether that exchange is needed after THIS launch (deep ghost zones let a kernel skip some)
-    bool iterTakesMail = false;       // set by pcgIteration: its kernels can read the previous launch's sums from a posted all-reduce (PcgIterArgs::mail)
-    // Before the first launch of a loop: would pcgIteration's kernels carry out a planned post themselves and poll the mailbox (PcgIterArgs::post / mail)?
-    virtual bool iterPostsItself(bool /*lm*/) const { return false; }
+    // Before the first launch of a Gauss-Newton (lm = false) or Levenberg-Marquardt loop: what kind of loop pcgIteration would run for the plan as it stands
+    virtual IterTraits iterTraits(bool /*lm*/) const { return IterTraits{}; }
     virtual ~EnergyOps() {}
     void addUnknown(int param, long elems, int channels) {
         unknowns.push_back({param, elems, channels, nScalars});
@@ -116,14 +135,8 @@ struct EnergyOps {
     // kernel set whose bind() derives device-side auxiliaries ONLY from inputs that are not unknowns (flag images, edge lists ...) may say so here, and the solver binds once
     // per solve instead of once per step.  Opt_ProblemStep called by itself always binds.
     virtual bool bindInvariantDuringSolve() const { return false; }
-    // pcgIteration kept the search directions in buffers of its own: where p of the launch issued last lives (nullptr: in the caller's pNew)
-    virtual const T* iterCurrentP() const { return nullptr; }
-    // LM loop: did the launch issued last write deltaOut (a kernel set that pairs its delta updates writes it every second launch) ...
-    virtual bool iterWroteDelta() const { return true; }
-    // ... and the term such a launch left owed, added to `delta` in place (issuedBeyond: launches issued after the one meant -- the solver's speculative next launch)
-    virtual void iterFlushDelta(T* /*delta*/, int /*issuedBeyond*/, LaunchCtx&) {}
-    // ... or handed to a solver kernel that adds it in its own pass: *p, *alpha[0] (false: nothing owed)
-    virtual bool iterOwedTerm(int /*issuedBeyond*/, const T** /*p*/, const T** /*alpha*/) const { return false; }
+    // LM loop: delta += alpha[0] * p in place, for the term a launch left owed (PcgIterResult::owedP / owedAlpha); only asked of the kernel set that reported one
+    virtual void addOwedTerm(T* /*delta*/, const T* /*p*/, const T* /*alpha*/, LaunchCtx&) {}
     virtual T* unknownPtr(int img) const = 0;
     virtual void precompute(LaunchCtx&) {}                                   // ComputedArrays (solver.t:607-614)
     // partial sums of 1/2 sum r^2 over non-excluded, owned elements (solver.t:580-592, 715-725)
@@ -155,7 +168,7 @@ struct EnergyOps {
     // Optional: the end of a single-kernel Gauss-Newton loop in one pass over the unknowns -- whatever pcgFinish would still add to delta, the last iteration's
     // delta += alpha p (alpha = sum aNum / sum aDen, guarded) and PCGLinearUpdate X += delta.  delta itself is dead afterwards and need not be written.
     // true: the unknowns are updated (the solver skips pcgFinish, the last PCGStep2 and PCGLinearUpdate).
-    virtual bool finishUpdate(const T* /*pPrev*/, const T* /*pLast*/, const T* /*delta*/, const Reduction& /*aNum*/, const Reduction& /*aDen*/, LaunchCtx&) { return false; }
+    virtual bool finishUpdate(const T* /*delta*/, const Reduction& /*aNum*/, const Reduction& /*aDen*/, LaunchCtx&) { return false; }
     // Optional: one WHOLE Gauss-Newton PCG iteration as a single kernel (see PcgIterArgs and solver.hip).
     virtual bool pcgIteration(const PcgIterArgs<T>& /*args*/, LaunchCtx&) { return false; }
     // Optional (single GPU; Gauss-Newton also on row slabs): the WHOLE linear solve -- lIterations PCG iterations (solverGPUGaussNewton.t:1056-1092) from r = r_0, p = M r_0 as PCGInit1
@@ -195,16 +208,10 @@ struct EnergyOps {
     virtual bool supportsDeferredSteps() const { return false; }
     // pcgIteration takes delta from its arguments at every launch and keeps no pointer to it: the solver may move the vector between two launches (PcgSolver::deltaTrial)
     virtual bool deltaMovable() const { return false; }
-    // Slab mode, before the loop: will pcgIteration accept the launches?  (The solver refreshes the ghost rows of r_0, p_0 and M for that loop only: the
-    // three-kernel loop relies on r being 0 on ghost rows -- its flat sums run over them.)
-    virtual bool slabIterationAvailable() const { return true; }
-    // Slab mode, after a pcgIteration launch with iterStateExchange: which vectors (solver layout) carry the state whose ghost rows the neighbours
-    // must refresh.  0 = the rNew / pNew the launch was given; a kernel set that keeps its loop state in buffers of its own lists them here.
-    virtual int iterExchangeVectors(T** /*out4*/) { return 0; }
     // Called once after the last pcgIteration of a linear solve, before the solver adds the last term alpha p to delta:
-    // lets a kernel set that defers part of its delta update apply what is left.  pPrev = the p buffer the last launch read.
+    // lets a kernel set that defers part of its delta update apply what is left.
     // Returns where the search direction of the last launch lives if the kernel set kept it in a buffer of its own (nullptr: in the pNew it was given).
-    virtual const T* pcgFinish(const T* /*pPrev*/, T* /*delta*/, LaunchCtx&) { return nullptr; }
+    virtual const T* pcgFinish(T* /*delta*/, LaunchCtx&) { return nullptr; }
     // Optional block-local solver (kind "patchGaussNewtonGPU", OptAmd.h): one additive-Schwarz sweep of LDS-resident patch PCG solves over
     // a tiling shifted by (fx, fy) patch widths, nPatchIters inner iterations each, applied to the unknowns directly; patchFinish is called
     // after the last sweep of a step and must leave the result in the caller's unknown buffers.  false = the energy has no such kernel.

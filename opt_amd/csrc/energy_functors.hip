@@ -226,7 +226,7 @@ struct OpticalFlowOps : StencilOps<T, OpticalFlowE<T>> {
         if (a.first) { ScopedKernel k(ctx, "operatorCoefficients"); flow_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e, coef); }
         return march.launch(FlowMarchOp<T>{this->e.w_fit, this->e.w_reg}, this->e.W, this->e.H, nullptr, this->cus, a, ctx, coef);
     }
-    const T* pcgFinish(const T*, T* delta, LaunchCtx& ctx) override { return march.finish(delta, 2L * this->e.W * this->e.H, this->cus, ctx); }
+    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, 2L * this->e.W * this->e.H, this->cus, ctx); }
     // ---- the whole Gauss-Newton linear solve on chip (stencil_onchip.h); the operator's per-pixel coefficient is formed first, as for the marching loop ----
     OnchipMarch<T> oc;
     bool onChipWithoutPreconditioner() const override { return true; }
@@ -289,7 +289,7 @@ struct IntrinsicOps : StencilOps<T, IntrinsicE<T>> {
         if (a.first) { ScopedKernel k(ctx, "operatorCoefficients"); intrinsic_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e.aux, coef, n); }
         return march.launch(IntrinsicMarchOp<T>{this->e.w_fit, this->e.w_regA, this->e.w_regS}, this->e.W, this->e.H, nullptr, this->cus, a, ctx, coef);
     }
-    const T* pcgFinish(const T*, T* delta, LaunchCtx& ctx) override { return march.finish(delta, 4L * this->e.W * this->e.H, this->cus, ctx); }
+    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, 4L * this->e.W * this->e.H, this->cus, ctx); }
     // ---- the whole linear solve on chip (stencil_onchip.h); the operator's coefficients are repacked first, as for the marching loop ----
     OnchipMarch<T> oc;
     bool onChipWithoutPreconditioner() const override { return true; }

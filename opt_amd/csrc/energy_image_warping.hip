@@ -21,6 +21,7 @@
 #include "iw_device.h"
 #include "iw_step.h"
 #include "iw_iter.h"
+#include "pcg_ring.h"
 #include "iw_onchip.h"
 #include <cstdint>
 
@@ -56,8 +57,7 @@ struct ImageWarpingOps : EnergyOps<T> {
     }
     ~ImageWarpingOps() override {
         (void)hipHostFree(hNotLattice); (void)hipEventDestroy(bindEvent);
-        for (T* b : ring) if (b) (void)hipFree(b);
-        (void)hipFree(A.flags); (void)hipFree(A.cs); if (alphaSlots) (void)hipFree(alphaSlots); (void)hipFree(dNotLattice);
+        (void)hipFree(A.flags); (void)hipFree(A.cs); (void)hipFree(dNotLattice);
         if (lmQState) (void)hipFree(lmQState);
     }
     int flatGrid(long n) const { return (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, std::min<long>(kMaxPartials, (long)cus * 8))); }
@@ -130,9 +130,8 @@ struct ImageWarpingOps : EnergyOps<T> {
     }
 
     // ---- once per Gauss-Newton step ----------------------------------------------------------------------------------------------------------------------------
-    bool fastGN() const {      // single GPU, vectors below 4 GiB (buffer-descriptor offsets are 32-bit): the marching PCGInit1 and the single-kernel / on-chip loops
-        return !this->slab.active && (unsigned long long)A.W * A.H * 3ull * sizeof(T) < (1ull << 32);
-    }
+    bool fits32() const { return (unsigned long long)A.W * A.H * 3ull * sizeof(T) < (1ull << 32); }      // vectors below 4 GiB: buffer-descriptor offsets are 32-bit
+    bool fastGN() const { return !this->slab.active && fits32(); }      // single GPU: the marching PCGInit1 and the single-kernel / on-chip loops
     T *initR = nullptr, *initP = nullptr; Reduction* initRed = nullptr; bool initHint = false, initPending = false, deltaZero = false;
     void launchJtf(bool lat, LaunchCtx& ctx, Reduction* cost = nullptr, const JtfLm<T>* lmInit = nullptr) {
         ScopedKernel k(ctx, cost ? "computeCost+PCGInit1" : "PCGInit1");
@@ -274,10 +273,25 @@ struct ImageWarpingOps : EnergyOps<T> {
     }
     static int iterBlock(bool lat, bool lmLoop) { return sizeof(T) == 8 ? 256 : lat ? 768 : lmLoop ? 512 : 768; }      // IterBlk<T, LATTICE, PRE, LM>::value of iterKernel's choice
     int occIter[4] = {0, 0, 0, 0};
-    int iterFlip = 0, sinceExchange = 0, iterIndex = 0;
-    bool deferredTerm = false, lastLoopRfree = false, lastLoopLmRing = false, lastWroteDelta = true; int sinceTrueR = 0, lmPrN = 0; double* lmQState = nullptr;
-    const T* owedP[2] = {nullptr, nullptr};
-    T* ring[3] = {nullptr, nullptr, nullptr}; const T* r0Ptr = nullptr; T* alphaSlots = nullptr;
+    // The loop's state: the ring (Gauss-Newton, and LM on a unit lattice) and what is image_warping's own, reset at the first launch of a linear solve
+    PcgRing<T> ring; double* lmQState = nullptr;
+    struct IterLoop {
+        bool gn = false, lmRing = false;      // which loop the launches belong to (neither: LM with a general UrShape, which keeps its vectors in the solver's buffers)
+        int sinceExchange = 0;                // slab mode: launches since the ghost rows were last exchanged
+        int lmPrN = 0;                        // lmRing: number of p . r partials the previous launch left
+    } loop;
+    // Would pcgIteration run the loop for the plan as it stands (given a preconditioner, which this energy always has)?
+    // A p is recomputed, not stored, so a slab needs two ghost rows (one for each stencil evaluation) -- with one the solver runs the three-kernel loop; the LM variant is single-GPU.
+    bool iterAccepts(bool lmLoop) const { return fits32() && (!this->slab.active || (this->slab.ghost >= 2 && !lmLoop)); }
+    IterTraits iterTraits(bool lmLoop) const override {
+        IterTraits t;
+        const bool ok = iterAccepts(lmLoop);
+        t.stateExchange = ok;                 // the ghost rows of the loop state come from the neighbours after a launch
+        t.takesMail = ok && !lmLoop;          // the prologue can poll a posted all-reduce ...
+        t.postsItself = ok && !lmLoop && this->slab.active;      // ... and the last workgroup posts this launch's
+        t.slabAvailable = ok;
+        return t;
+    }
     // What the loops do before their first launch: this bind's lattice verdict (the marching bind does not block for it); a PCGInit1 that ran on the previous
     // verdict and guessed "lattice" for an input that is none is redone.
     void beginLoop(LaunchCtx& ctx) {
@@ -285,30 +299,23 @@ struct ImageWarpingOps : EnergyOps<T> {
         if (initPending) { if (initHint && !lattice) launchJtf(false, ctx); initHint = lattice; initPending = false; }
     }
     bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
-        // A p is recomputed, not stored, so a slab needs two ghost rows (one for each stencil evaluation); with one the solver runs the three-kernel loop.
-        if (!a.pre || (this->slab.active && this->slab.ghost < 2)) return false;
-        if ((unsigned long long)A.W * A.H * 3ull * sizeof(T) >= (1ull << 32)) return false;      // 32-bit buffer offsets
         const bool lmLoop = a.CtC != nullptr;
-        if (lmLoop && this->slab.active) return false;      // the LM variant is single-GPU
-        if (a.first) beginLoop(ctx);
-        this->iterStateExchange = true;      // slab mode: the ghost rows of the loop state come from the neighbours after a launch
-        this->iterTakesMail = !lmLoop;       // the prologue can poll a posted all-reduce
+        if (!a.pre || !iterAccepts(lmLoop)) return false;
+        if (a.first) { beginLoop(ctx); loop = IterLoop{}; }
+        PcgIterResult<T>& res = *a.result;
         // With g >= 2 ghost rows whose state is current to depth v, a launch can also update the ghost rows to depth v - 1 (their A p needs one more row on either
         // side) and its sums need depth 2; so after an exchange at depth g the slab runs g - 1 launches before it needs the neighbours again, launch j = 1 .. g - 1
         // of the period updating g - j ghost rows (none in the last one: they are about to be overwritten).
         int ext = 0;
-        this->iterExchangeDue = true;
         if (this->slab.active) {
-            if (a.first) sinceExchange = 0;
-            const int period = std::max(1, std::min(this->slab.ghost - 1, maxExchangePeriod)), j = sinceExchange + 1;
+            const int period = std::max(1, std::min(this->slab.ghost - 1, maxExchangePeriod)), j = loop.sinceExchange + 1;
             const bool due = j >= period;
             ext = due ? 0 : this->slab.ghost - j;
-            sinceExchange = due ? 0 : j;
-            this->iterExchangeDue = due;
+            loop.sinceExchange = due ? 0 : j;
+            res.exchangeDue = due;
         }
         IWArgs<T> Ax = A;                   // what the kernel sees: the rows it updates
         Ax.yBegin = std::max(0, A.yBegin - ext); Ax.yEnd = std::min(A.H, A.yEnd + ext);
-        if (a.first) { iterFlip = 0; iterIndex = 0; }      // every linear solve starts top-down, so a solve is reproducible whatever ran before it
         const int blk = iterBlock(lattice, lmLoop), L = (lmLoop ? 2 : 0) + (lattice ? 1 : 0);
         if (occIter[L] == 0) {
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occIter[L], iterKernel(lattice, lmLoop, false, 0), blk, 0));
@@ -317,43 +324,38 @@ struct ImageWarpingOps : EnergyOps<T> {
         const int gx = divUp(A.W, (blk / kWave) * kSpan2);
         int gy, rowsPerGroup;
         splitRows(Ax.yEnd - Ax.yBegin, gx, cus * occIter[L], gy, rowsPerGroup);
-        // Gauss-Newton: delta every second launch, and no residual vector -- the state is a ring of three p buffers (ring[j % 3] holds p_j; the first two
-        // launches read the solver's r_0).  LM on a unit lattice (round 6) runs on the same ring -- the two launches behind PCGInit1 or a split residual reset read the true r the
-        // solver holds -- and takes Q from the CG recurrence (iw_iter.h), so neither r nor b moves; delta is updated in every launch (an early-out must find it complete).
-        // LM with a general UrShape keeps r, CtC, M and b in memory.
+        // Gauss-Newton: delta every second launch, and no residual vector -- the loop runs on the ring (pcg_ring.h; the first two launches read the solver's r_0).
+        // LM on a unit lattice (round 6) runs on the same ring -- the two launches behind PCGInit1 or a split residual reset read the true r the
+        // solver holds -- and takes Q from the CG recurrence (iw_iter.h), so neither r nor b moves; an early-out must find delta complete, so what a deferring
+        // launch owes is reported (PcgIterResult::owedP) and the solver has it added before a reset, an early-out or the end of the loop.
+        // LM with a general UrShape keeps r, CtC, M and b in memory and its vectors in the solver's buffers.
         const bool gn = !lmLoop, lmRing = lmLoop && lattice;
-        const T *rOldPtr = a.rOld, *pOldPtr = a.pOld; T* pNewPtr = a.pNew; int rfreeFlag = 0, deltaMode = 0; const T* alphaIn = nullptr; T* alphaOut = nullptr;
+        loop.gn = gn; loop.lmRing = lmRing;
+        typename PcgRing<T>::Launch R{};
         if (gn || lmRing) {
-            const size_t bytes = ((size_t)A.W * A.H * 3 + 3) / 4 * 4 * sizeof(T);      // padded like the solver's vectors: its flat kernels read whole 16-byte packs of the last p
-            for (int j = 0; j < 3; ++j) if (!ring[j]) { HIP_CHECK(hipMalloc((void**)&ring[j], bytes)); HIP_CHECK(hipMemsetAsync(ring[j], 0, bytes, ctx.stream)); }
-            if (a.first || a.afterReset) { r0Ptr = a.rOld; sinceTrueR = 0; }      // the solver swaps its r buffers after every launch; this one keeps the true r until the second launch has read it
-            const int k = iterIndex;
-            pOldPtr = k == 0 ? a.pOld : ring[(k - 1) % 3];
-            rOldPtr = sinceTrueR <= 1 ? r0Ptr : ring[(k - 2) % 3];
-            pNewPtr = ring[k % 3];
-            rfreeFlag = sinceTrueR <= 1 ? 2 : 1;
-            if (!alphaSlots) { HIP_CHECK(hipMalloc((void**)&alphaSlots, 4 * sizeof(T))); HIP_CHECK(hipMemsetAsync(alphaSlots, 0, 4 * sizeof(T), ctx.stream)); }   // [0,1] alpha, [2,3] beta, ping-pong
-            deltaMode = (sinceTrueR >= 2 && sinceTrueR % 2 == 0) ? 1 : 2;      // the launch behind PCGInit1 / a reset has nothing to apply; odd launches defer
-            // what this launch leaves owed to delta (LM: the solver has it added before a reset, an early-out or the end of the loop -- iterFlushDelta)
-            owedP[k & 1] = (lmRing && sinceTrueR % 2 == 1) ? pOldPtr : nullptr; lastWroteDelta = !lmRing || deltaMode == 1;
-            ++sinceTrueR;
-            alphaOut = alphaSlots + (k & 1); alphaIn = alphaSlots + ((k & 1) ^ 1);
+            ring.allocate((size_t)A.W * A.H * 3, ctx.stream);
+            R = ring.next(a.first != 0, a.afterReset != 0, a.rOld, a.pOld);
+        } else { R.flip = ring.nextSweep(a.first != 0); R.pOld = a.pOld; R.rOld = a.rOld; R.pNew = a.pNew; }
+        if (gn) {      // slab mode: the two newest search directions carry the state (launch 1 reads the solver's r_0, whose ghost rows were exchanged before the loop, and p_0)
+            res.exchange[0] = R.pNew; res.nExchange = 1;
+            if (R.k >= 1) { res.exchange[1] = const_cast<T*>(R.pOld); res.nExchange = 2; }
         }
-        if (lmRing && !lmQState) {      // the running Q and the two sets of p . r partials (this launch's / the previous launch's)
-            HIP_CHECK(hipMalloc((void**)&lmQState, sizeof(double) * (1 + 2 * (size_t)kMaxPartials)));
-            HIP_CHECK(hipMemsetAsync(lmQState, 0, sizeof(double) * (1 + 2 * (size_t)kMaxPartials), ctx.stream));
+        if (lmRing) {
+            res.p = R.pNew; res.wroteDelta = R.deltaMode == 1;
+            if (R.owedP) { res.owedP = R.owedP; res.owedAlpha = R.alphaOut; }
+            if (!lmQState) {      // the running Q and the two sets of p . r partials (this launch's / the previous launch's)
+                HIP_CHECK(hipMalloc((void**)&lmQState, sizeof(double) * (1 + 2 * (size_t)kMaxPartials)));
+                HIP_CHECK(hipMemsetAsync(lmQState, 0, sizeof(double) * (1 + 2 * (size_t)kMaxPartials), ctx.stream));
+            }
         }
-        if (!gn && !lmRing) lastWroteDelta = true;
-        lastLoopRfree = gn; lastLoopLmRing = lmRing;
-        deferredTerm = gn && iterIndex >= 1 && iterIndex % 2 == 1;            // after an odd launch alpha_{k-1} p_{k-1} is still owed (pcgFinish / finishUpdate)
         IterK<T> K{};
-        K.rOld = rOldPtr; K.pOld = pOldPtr; K.rNew = a.rNew; K.pNew = pNewPtr; K.delta = a.delta; K.deltaOut = a.deltaOut ? a.deltaOut : a.delta;
-        K.pre = a.pre; K.first = a.first; K.deltaMode = deltaMode; K.alphaIn = alphaIn; K.alphaOut = alphaOut; K.rfree = rfreeFlag;
+        K.rOld = R.rOld; K.pOld = R.pOld; K.rNew = a.rNew; K.pNew = R.pNew; K.delta = a.delta; K.deltaOut = a.deltaOut ? a.deltaOut : a.delta;
+        K.pre = a.pre; K.first = a.first; K.deltaMode = R.deltaMode; K.alphaIn = R.alphaIn; K.alphaOut = R.alphaOut; K.rfree = R.rfree;
         K.CtC = a.CtC; K.b = a.b; K.q = a.q ? a.q->partials : nullptr; K.qTag = a.qTag; K.afterReset = a.afterReset;
         K.betaNum = a.betaNum.partials; K.nBetaNum = a.betaNum.n; K.betaDen = a.betaDen.partials; K.nBetaDen = a.betaDen.n;
         if (lmRing) {
             K.qState = lmQState; K.qInit = a.qInit;
-            K.pr = lmQState + 1 + (size_t)(iterIndex & 1) * kMaxPartials; K.prPrev = lmQState + 1 + (size_t)((iterIndex & 1) ^ 1) * kMaxPartials; K.nPr = lmPrN;
+            K.pr = lmQState + 1 + (size_t)(R.k & 1) * kMaxPartials; K.prPrev = lmQState + 1 + (size_t)((R.k & 1) ^ 1) * kMaxPartials; K.nPr = loop.lmPrN;
         }
         K.lmRadius = a.lmRadius; K.lmMin = a.lmMinDiag; K.lmMax = a.lmMaxDiag;
         K.aNumPrev = a.aNumPrev.partials; K.aDenPrev = a.aDenPrev.partials; K.s2Prev = a.s2Prev.partials; K.s3Prev = a.s3Prev.partials;
@@ -364,81 +366,44 @@ struct ImageWarpingOps : EnergyOps<T> {
         for (int t = 0; t < 16; ++t) K.post.dst[t] = a.post.dst[t];
         K.post.world = a.post.world; K.post.tag = a.post.tag; K.post.ticket = a.post.ticket;
         K.deltaZero = 0;
-        if (deltaZero && !a.first && deltaMode != 2 && gn) { K.deltaZero = 1; deltaZero = false; }      // this launch writes every pixel's delta: from here on the buffer is real
+        if (deltaZero && !a.first && R.deltaMode != 2 && gn) { K.deltaZero = 1; deltaZero = false; }      // this launch writes every pixel's delta: from here on the buffer is real
         {
             ScopedKernel k(ctx, "PCGIteration");
             int rpg = rowsPerGroup, gxa = gx, gya = gy;
             void* kargs[] = {(void*)&Ax, (void*)&K, (void*)&rpg, (void*)&gxa, (void*)&gya};
             // from the third launch of a Gauss-Newton solve on the launch state alternates between two values: compiled in
-            const int mode = ((gn || lmRing) && rfreeFlag == 1 && !a.first && !a.afterReset && !K.deltaZero) ? (deltaMode == 2 ? 1 : 2) : 0;
-            HIP_CHECK(hipLaunchKernel(iterKernel(lattice, lmLoop, iterFlip != 0, mode), dim3(gx * gy), dim3(blk), kargs, 0, ctx.stream));
+            const int mode = ((gn || lmRing) && R.rfree == 1 && !a.first && !a.afterReset && !K.deltaZero) ? (R.deltaMode == 2 ? 1 : 2) : 0;
+            HIP_CHECK(hipLaunchKernel(iterKernel(lattice, lmLoop, R.flip != 0, mode), dim3(gx * gy), dim3(blk), kargs, 0, ctx.stream));
         }
-        iterFlip ^= 1;      // successive launches sweep top-down / bottom-up: a launch starts on the rows the previous one left in the caches
-        ++iterIndex;
         a.aNum->n = a.aDen->n = a.s2->n = a.s3->n = gx * gy;
         if (a.q) a.q->n = lmRing ? 1 : gx * gy;      // (the recurrence's Q is one value, published by workgroup 0)
-        lmPrN = gx * gy;
+        loop.lmPrN = gx * gy;
         return true;
     }
-    // Where p of the last launch lives when the loop keeps its own buffers (the LM loop's reset and tail kernels read it)
-    const T* iterCurrentP() const override { return lastLoopLmRing && iterIndex >= 1 ? ring[(iterIndex - 1) % 3] : nullptr; }
-    bool iterWroteDelta() const override { return lastWroteDelta; }
-    // delta += the term the launch `issuedBeyond` before the one issued last left owed (a deferring launch of the paired LM loop), if any
-    bool iterOwedTerm(int issuedBeyond, const T** p, const T** alpha) const override {
-        const int idx = iterIndex - 1 - issuedBeyond;
-        if (!lastLoopLmRing || idx < 0 || !owedP[idx & 1]) return false;
-        *p = owedP[idx & 1]; *alpha = alphaSlots + (idx & 1);
-        return true;
-    }
-    void iterFlushDelta(T* delta, int issuedBeyond, LaunchCtx& ctx) override {
-        const T *p = nullptr, *alpha = nullptr;
-        if (!iterOwedTerm(issuedBeyond, &p, &alpha)) return;
+    // delta += the term a deferring launch of the paired LM loop left owed
+    void addOwedTerm(T* delta, const T* p, const T* alpha, LaunchCtx& ctx) override {
         ScopedKernel k(ctx, "PCGStep2_delta");
         const long n = 3L * A.W * A.H;
-        iw_axpyDeferred<T><<<flatGrid(n), kBlock, 0, ctx.stream>>>(delta, p, alpha, n);
+        axpyDeferred<T><<<flatGrid(n), kBlock, 0, ctx.stream>>>(delta, p, alpha, n);
     }
-    // Slab mode, after launch iterIndex - 1: the vectors whose ghost rows the neighbours must refresh -- the two newest search directions of the ring.
-    int iterExchangeVectors(T** out) override {
-        if (!lastLoopRfree || iterIndex < 1) return 0;
-        out[0] = ring[(iterIndex - 1) % 3];
-        if (iterIndex < 2) return 1;                      // launch 1 reads the solver's r_0 (ghost rows exchanged before the loop) and p_0
-        out[1] = ring[(iterIndex - 2) % 3];
-        return 2;
-    }
-    // After the last launch L-1 of a linear solve.  If it was an odd launch, the term alpha_{L-2} p_{L-2} was deferred: its alpha sits in the slot that launch
+    // After the last launch L-1 of a Gauss-Newton linear solve.  If it was an odd launch, the term alpha_{L-2} p_{L-2} was deferred: its alpha sits in the slot that launch
     // wrote.  The solver then adds alpha_{L-1} p_{L-1}; returns where p_{L-1} lives.
-    const T* pcgFinish(const T* pPrev, T* delta, LaunchCtx& ctx) override {
+    const T* pcgFinish(T* delta, LaunchCtx& ctx) override {
         if (deltaZero) { HIP_CHECK(hipMemsetAsync(delta, 0, ((size_t)A.W * A.H * 3 + 3) / 4 * 4 * sizeof(T), ctx.stream)); deltaZero = false; }      // the generic tail reads it
-        const T* pLast = nullptr;
-        if (lastLoopRfree && iterIndex >= 1) {
-            pLast = ring[(iterIndex - 1) % 3];
-            if (iterIndex >= 2) pPrev = ring[(iterIndex - 2) % 3];
-        }
-        if (!deferredTerm) return pLast;
-        ScopedKernel k(ctx, "PCGStep2_delta");
+        if (!loop.gn) return nullptr;
         const long n = 3L * A.W * A.H;
-        iw_axpyDeferred<T><<<flatGrid(n), kBlock, 0, ctx.stream>>>(delta, pPrev, alphaSlots + ((iterIndex - 1) & 1), n);
-        deferredTerm = false;
-        return pLast;
+        return ring.finish(delta, n, flatGrid(n), ctx);
     }
     // Last delta terms + X += delta in one pass (iw_finishUpdate), single GPU.
-    bool finishUpdate(const T* pPrev, const T* pLast, const T* delta, const Reduction& aNum, const Reduction& aDen, LaunchCtx& ctx) override {
-        if (this->slab.active) return false;
-        if (lastLoopRfree && iterIndex >= 1) {
-            pLast = ring[(iterIndex - 1) % 3];
-            if (iterIndex >= 2) pPrev = ring[(iterIndex - 2) % 3];
-        }
+    bool finishUpdate(const T* delta, const Reduction& aNum, const Reduction& aDen, LaunchCtx& ctx) override {
+        if (this->slab.active || !loop.gn) return false;
         ScopedKernel k(ctx, "PCGLinearUpdate");
         const long N = (long)A.W * A.H;
-        iw_finishUpdate<T><<<flatGrid(N), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.Offset), const_cast<T*>(A.Angle), deltaZero ? nullptr : delta, pLast, deferredTerm ? pPrev : nullptr,
-                                                                   alphaSlots ? alphaSlots + ((iterIndex - 1) & 1) : nullptr, N, aNum.partials, aNum.n, aDen.partials, aDen.n);
-        deferredTerm = false; deltaZero = false;
+        iw_finishUpdate<T><<<flatGrid(N), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.Offset), const_cast<T*>(A.Angle), deltaZero ? nullptr : delta, ring.pLast(), ring.termOwed() ? ring.pPrev() : nullptr,
+                                                                   ring.alphaSlot(ring.iterIndex - 1), N, aNum.partials, aNum.n, aDen.partials, aDen.n);
+        ring.settled(); deltaZero = false;
         return true;
     }
-    bool iterPostsItself(bool lmLoop) const override {      // would pcgIteration accept the launch (and so carry out a planned post)?  Same conditions as its refusals above.
-        return !lmLoop && this->slab.active && this->slab.ghost >= 2 && (unsigned long long)A.W * A.H * 3ull * sizeof(T) < (1ull << 32);
-    }
-    bool slabIterationAvailable() const override { return this->slab.ghost >= 2 && (unsigned long long)A.W * A.H * 3ull * sizeof(T) < (1ull << 32); }
     bool supportsSlab() const override { return true; }
     long rowScalars(int img) const override { return (long)A.W * (img == 0 ? 2 : 1); }
 
@@ -490,14 +455,14 @@ struct ImageWarpingOps : EnergyOps<T> {
     bool slabOnChipAvailable(int L) override {      // (row slabs: the lattice verdict of this bind is already known, bind() read it back)
         int tX, tY;
         if (!(guard.usable() && L > 0 && this->slab.active && this->slab.ghost >= 2 && this->onChipPlan && lattice &&
-              (unsigned long long)A.W * A.H * 3ull * sizeof(T) < (1ull << 32) && ocSelect(tX, tY) != nullptr)) return false;
+              fits32() && ocSelect(tX, tY) != nullptr)) return false;
         // ... and the communicator could plan it (count = 0: a dry query -- its sticky error state and the capacity of its edge boxes -- so that a "no" is part of the vote)
         return this->onChipPlan(this->onChipCtx, 4, 0, tX, 3L * kOcTileW * (long)(sizeof(T) / 4), nullptr) != 0;
     }
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lmArgs, LaunchCtx& ctx) override {
         const bool slabMode = this->slab.active;
         if (lmArgs && (slabMode || traceDev || lmArgs->resetPeriod < 1)) return false;      // the LM variants are single-GPU
-        if (!guard.usable() || L <= 0 || (unsigned long long)A.W * A.H * 3ull * sizeof(T) >= (1ull << 32)) return false;
+        if (!guard.usable() || L <= 0 || !fits32()) return false;
         if (slabMode && (traceDev || !slabOnChipAvailable(L))) return false;
         resolveLattice();
         if (initPending && initHint && !lattice) { launchJtf(false, ctx); initHint = false; }      // PCGInit1 ran on the previous bind's verdict (see beginLoop)

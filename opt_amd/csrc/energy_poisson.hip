@@ -294,7 +294,7 @@ struct PoissonOps : EnergyOps<T> {
         if (!singleKernel || a.pre || a.CtC) return false;      // Gauss-Newton only: the Levenberg-Marquardt loop keeps the generic kernels
         return march.launch(PoissonMarchOp<T>{}, A.W, A.H, flags, cus, a, ctx);
     }
-    const T* pcgFinish(const T*, T* delta, LaunchCtx& ctx) override { return march.finish(delta, 4L * A.W * A.H, cus, ctx); }
+    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, 4L * A.W * A.H, cus, ctx); }
     bool deltaMovable() const override { return !this->slab.active; }      // (the march takes delta from its arguments at every launch: PcgSolver::deltaTrial)
     // ---- the whole Gauss-Newton linear solve on chip (stencil_onchip.h) ----
     OnchipMarch<T> oc;
@@ -411,7 +411,7 @@ struct LaplacianOps : EnergyOps<float> {
         if (a.pre || a.CtC) return false;
         return march.launch(LaplacianMarchOp{}, A.W, A.H, nullptr, cus, a, ctx);
     }
-    const float* pcgFinish(const float*, float* delta, LaunchCtx& ctx) override { return march.finish(delta, (long)A.W * A.H, cus, ctx); }
+    const float* pcgFinish(float* delta, LaunchCtx& ctx) override { return march.finish(delta, (long)A.W * A.H, cus, ctx); }
     bool deltaMovable() const override { return !this->slab.active; }
     OnchipMarch<float> oc;      // the whole Gauss-Newton linear solve on chip (stencil_onchip.h)
     bool onChipWithoutPreconditioner() const override { return true; }

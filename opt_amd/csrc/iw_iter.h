@@ -24,7 +24,7 @@
 //     Thread 0 of workgroup 0 keeps the running Q (IterK::qState) and publishes it where the host's early-out test polls (one tagged word pair instead of one per
 //     workgroup, and at the START of the launch).  A reset re-anchors it to the host's direct sum (IterK::qInit).  With Q off delta's back, delta is paired as in
 //     Gauss-Newton (written by every second launch into the other buffer, so an early-out still finds the old one; the term a deferring launch owes is added by
-//     the solver before a reset, an early-out or the end of the loop: EnergyOps::iterFlushDelta).  89 -> 53 B/pixel.
+//     the solver before a reset, an early-out or the end of the loop: PcgIterResult::owedP, EnergyOps::addOwedTerm).  89 -> 53 B/pixel.
 #pragma once
 #include "iw_device.h"
 

@@ -3,7 +3,7 @@
 //   one thread per pixel (row slabs, probes, LM):  iw_flags, iw_cossin, iw_cost, iw_evalJTF, iw_checkLattice, iw_modelCost, iw_zeroGhost
 //   row-marching (single GPU):                      iw_bindMarch (flags + unit-lattice verdict), iw_jtfMarch (PCGInit1 + PCGInit1_Finish), iw_costMarch
 //   row-marching stencil:                           iw_applyJTJ (PCGStep1, optionally with the previous PCGStep3 fused in)
-//   flat passes:                                    iw_finishUpdate (last delta terms + PCGLinearUpdate), iw_axpyDeferred
+//   flat passes:                                    iw_finishUpdate (last delta terms + PCGLinearUpdate); the deferred delta term alone: pcg_ring.h axpyDeferred
 #pragma once
 #include "iw_device.h"
 
@@ -591,13 +591,6 @@ __global__ __launch_bounds__(kBlock) void iw_finishUpdate(T* __restrict__ XO, T*
         d.x = d.x + a1 * q.x; d.y = d.y + a1 * q.y; da = da + a1 * qa;
         xO[i] = V2<T>{x.x + d.x, x.y + d.y}; XA[i] = xa + da;
     }
-}
-
-// delta += alpha[0] * p over n scalars (the deferred term left over when the PCG loop ends on an odd launch)
-template <class T>
-__global__ __launch_bounds__(kBlock) void iw_axpyDeferred(T* __restrict__ delta, const T* __restrict__ p, const T* __restrict__ alpha, long n) {
-    const T a = alpha[0];
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) delta[i] = delta[i] + a * p[i];
 }
 
 // Is UrShape a unit lattice (U(x,y) - U(x+1,y) == (-1,0) and U(x,y) - U(x,y+1) == (0,-1) exactly)?  The reference

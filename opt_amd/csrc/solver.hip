@@ -163,7 +163,7 @@ __global__ __launch_bounds__(kBlock) void k_step2(T* __restrict__ delta, const T
 // deltaOut may be delta (in place) or another vector (the caller then decides later which of the two it keeps).  alphaNumerator is either a
 // finished total (aNumTotal, nNum == 0) or partial sums this kernel adds up itself -- the same sumPartials over kBlock threads as
 // k_finalizeSum, so the same bits, one launch less.
-// pOwed / alphaOwed (may be null): a term alphaOwed[0] * pOwed that an earlier launch left owed to delta (EnergyOps::iterOwedTerm) is added first -- the reference's
+// pOwed / alphaOwed (may be null): a term alphaOwed[0] * pOwed that an earlier launch left owed to delta (PcgIterResult::owedP) is added first -- the reference's
 // order of additions, one pass instead of two.
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_step2FirstHalf(const T* delta, T* deltaOut, const T* __restrict__ p, long nPacks, const double* __restrict__ aNumTotal,
@@ -755,8 +755,10 @@ struct PcgSolver : SolverBase {
         }
         int cur = 0;
         OptAmd_MailRef mail{nullptr, 0, 0, 0, 0, nullptr};      // where the next launch finds the previous launch's sums if they were posted, not reduced
+        const IterTraits traits = E->iterTraits(false);
         for (int lIter = 0; lIter < sp.lIterations; ++lIter) {
             PcgIterArgs<T> a{};
+            PcgIterResult<T> done; a.result = &done;
             a.rOld = r; a.ApOld = Ap_X; a.pOld = p; a.rNew = r2; a.ApNew = Ap2; a.pNew = p2; a.delta = delta; a.pre = preArg; a.first = lIter == 0;
             a.aNumPrev = prev[0]; a.aDenPrev = prev[1]; a.s2Prev = prev[2]; a.s3Prev = prev[3];
             a.aNum = &setS[cur][0]; a.aDen = &setS[cur][1]; a.s2 = &setS[cur][2]; a.s3 = &setS[cur][3];
@@ -764,17 +766,17 @@ struct PcgSolver : SolverBase {
             // the all-reduce of THIS launch's sums, carried out by the launch itself if the communicator can plan it and the kernel set can post
             bool planned = false;
             OptAmd_MailRef nextMail{nullptr, 0, 0, 0, 0, nullptr};
-            if (distributed && commExt.allReducePlan && lIter + 1 < sp.lIterations && !traceEnabled && E->iterPostsItself(false))
+            if (distributed && commExt.allReducePlan && lIter + 1 < sp.lIterations && !traceEnabled && traits.postsItself)
                 planned = commExt.allReducePlan(comm.ctx, 4, &a.post, &nextMail) != 0;
-            if (distributed && lIter > 0 && !E->iterStateExchange) exchangeVector(Ap_X);   // kernel with Ap in memory: r and p ghost rows are kept current by the kernel itself
+            if (distributed && lIter > 0 && !traits.stateExchange) exchangeVector(Ap_X);   // kernel with Ap in memory: r and p ghost rows are kept current by the kernel itself
             deltaTrial.beforeLaunch(*this, lIter); a.delta = delta;
             if (!E->pcgIteration(a, ctx)) { if (lIter == 0) return false; refusedMidLoop(); }
             std::swap(r, r2); std::swap(Ap_X, Ap2); std::swap(p, p2);
-            if (distributed && E->iterStateExchange && E->iterExchangeDue) {   // Ap-free kernel: the neighbours' edge rows of r_k and p_k, one grouped exchange
+            if (distributed && traits.stateExchange && done.exchangeDue) {   // Ap-free kernel: the neighbours' edge rows of r_k and p_k, one grouped exchange
                 std::vector<T*> bases;
-                T* vecs[4] = {r, p, nullptr, nullptr};
-                int nv = E->iterExchangeVectors(vecs);
-                if (nv == 0) nv = 2;
+                T* own[2] = {r, p};
+                T* const* vecs = done.nExchange ? done.exchange : own;
+                const int nv = done.nExchange ? done.nExchange : 2;
                 for (int v = 0; v < nv; ++v) for (size_t i = 0; i < E->unknowns.size(); ++i) bases.push_back(vecs[v] + E->unknowns[i].offset);
                 exchangeRows(bases);
             }
@@ -786,7 +788,7 @@ struct PcgSolver : SolverBase {
                 // by the flat kernel that closes the loop: those take the complete all-reduce.
                 bool posted = planned;
                 if (planned) mail = nextMail;
-                if (!posted && commExt.allReducePost && E->iterTakesMail && lIter + 1 < sp.lIterations && !traceEnabled) {
+                if (!posted && commExt.allReducePost && traits.takesMail && lIter + 1 < sp.lIterations && !traceEnabled) {
                     const double* ps[4]; int ns[4];
                     for (int i = 0; i < 4; ++i) { ps[i] = setS[cur][i].partials; ns[i] = setS[cur][i].n; }
                     posted = commExt.allReducePost(comm.ctx, ps, ns, 4, &mail, (void*)stream) != 0;
@@ -805,8 +807,8 @@ struct PcgSolver : SolverBase {
         }
         // the last iteration's delta += alpha p (PCGStep2, solver.t:461-462); r, z, p of that iteration are dead.  A kernel set may fold it, its own
         // deferred terms and PCGLinearUpdate into one pass over the unknowns (EnergyOps::finishUpdate).
-        if (!distributed && !traceEnabled && sp.lIterations > 0 && E->finishUpdate(p2, p, delta, prev[0], prev[1], ctx)) { unknownsUpdated = true; return true; }
-        const T* pLast = E->pcgFinish(p2, delta, ctx);
+        if (!distributed && !traceEnabled && sp.lIterations > 0 && E->finishUpdate(delta, prev[0], prev[1], ctx)) { unknownsUpdated = true; return true; }
+        const T* pLast = E->pcgFinish(delta, ctx);
         if (!pLast) pLast = p;
         finalizeLocal(prev[0], scal + 2);
         step2Delta(pLast, scal + 2, Reduction{}, prev[1]);
@@ -826,7 +828,8 @@ struct PcgSolver : SolverBase {
         Reduction bNumDirect{}, bDenDirect{};
         double qDirect = 0;                                         // Q as the last split residual reset summed it (PcgIterArgs::qInit of the restart launch)
         unsigned tagOf[2] = {0, 0};                                 // tag of the Q partials in redQ / redQ2
-        auto pNow = [&]() -> const T* { const T* own = E->iterCurrentP(); return own ? own : p; };      // p of the launch adopted last (a kernel set may keep the directions in buffers of its own)
+        PcgIterResult<T> issuedRes, adopted;                        // what the launch issued last / adopted last reported (they differ while a speculative launch is outstanding)
+        auto pNow = [&]() -> const T* { return adopted.p ? adopted.p : p; };      // p of the launch adopted last (a kernel set may keep the directions in buffers of its own)
         // One launch from the current state into the alternate buffers (r2, p2, delta2, setS[cur]); adopted later by pointer swaps.
         auto issue = [&](int k, bool restart) -> bool {
             PcgIterArgs<T> a{};
@@ -837,6 +840,7 @@ struct PcgSolver : SolverBase {
             if (taggedQ) { if (++launchTag == 0) ++launchTag; a.qTag = tagOf[k & 1] = launchTag; } else tagOf[k & 1] = 0;      // (0: this launch writes plain partials)
             a.lmRadius = trust_region_radius; a.lmMinDiag = min_lm_diagonal; a.lmMaxDiag = max_lm_diagonal;
             issuedRestart = restart;
+            issuedRes = PcgIterResult<T>{}; a.result = &issuedRes;
             return E->pcgIteration(a, ctx);
         };
         for (int lIter = 0; lIter < sp.lIterations; ++lIter) {
@@ -845,9 +849,8 @@ struct PcgSolver : SolverBase {
             // adopt launch lIter
             const bool appliedStep2 = lIter > 0 && !issuedRestart;    // it finished iteration lIter-1 (delta, r, z, p) and summed Q_{lIter-1}
             std::swap(r, r2); std::swap(p, p2); std::swap(Ap_X, Ap2);
-            if (appliedStep2 && E->iterWroteDelta()) std::swap(delta, delta2);      // (a kernel set that pairs its delta updates writes every second launch; what a deferring launch owes: flushOwed)
-            bool owedFlushed = false;
-            auto flushOwed = [&](int issuedBeyond) { if (!owedFlushed && appliedStep2) { E->iterFlushDelta(delta, issuedBeyond, ctx); owedFlushed = true; } };
+            adopted = issuedRes;
+            if (appliedStep2 && adopted.wroteDelta) std::swap(delta, delta2);      // (a kernel set that pairs its delta updates writes every second launch; what a deferring launch owes: adopted.owedP)
             for (int i = 0; i < 4; ++i) prev[i] = setS[cur][i];
             cur ^= 1;
             afterReset = false;
@@ -858,8 +861,7 @@ struct PcgSolver : SolverBase {
             const bool lastAndSilent = lIter + 1 >= sp.lIterations && verbosity == 0;
             auto resetKernels = [&](T* deltaOut) {
                 // (a term the adopted launch left owed goes in first, in the same pass; `delta` itself stays as it is: an early-out decided below flushes it there)
-                const T *pOwed = nullptr, *aOwed = nullptr;
-                if (appliedStep2 && !owedFlushed) (void)E->iterOwedTerm(0, &pOwed, &aOwed);
+                const T *pOwed = appliedStep2 ? adopted.owedP : nullptr, *aOwed = appliedStep2 ? adopted.owedAlpha : nullptr;
                 { ScopedKernel k(ctx, "PCGStep2_1stHalf");
                   k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, deltaOut, pNow(), nPacks, nullptr, prev[0].partials, prev[0].n, prev[1].partials, prev[1].n, pOwed, aOwed); }
                 if (lastAndSilent) return;
@@ -882,7 +884,7 @@ struct PcgSolver : SolverBase {
                 if (Q1 != Q1) {      // a tagged Q partial never arrived (pollTaggedSum said why): this iteration's test is skipped, Q0 stays the last known value, and the
                     taggedQ = false; //  plan reads Q through the stream (beginHostSum / endHostSum) from here on, so the later early-out tests are real again
                 } else {
-                    if (qEarlyOut(lIter, Q1, Q0, (T)sp.q_tolerance)) { flushOwed(issued ? 1 : 0); return true; }
+                    if (qEarlyOut(lIter, Q1, Q0, (T)sp.q_tolerance)) { if (adopted.owedP) E->addOwedTerm(delta, adopted.owedP, adopted.owedAlpha, ctx); return true; }
                     Q0 = Q1;
                 }
             }
@@ -902,9 +904,7 @@ struct PcgSolver : SolverBase {
             }
         }
         if (deltaOwed) {   // the last iteration's delta += alpha p; its r, z, p and Q are dead (the reference's last fetchQ can only break a finished loop)
-            const T *pOwed = nullptr, *aOwed = nullptr;
-            (void)E->iterOwedTerm(0, &pOwed, &aOwed);      // (... behind the term a deferring last launch left owed)
-            step2Delta(pNow(), nullptr, prev[0], prev[1], pOwed, aOwed);
+            step2Delta(pNow(), nullptr, prev[0], prev[1], adopted.owedP, adopted.owedAlpha);      // (... behind the term a deferring last launch left owed)
         }
         return true;
     }
@@ -1063,7 +1063,7 @@ struct PcgSolver : SolverBase {
                 if (oneKernelLM && !distributed && !traceEnabled && (tryOnChip(preArg, &la) || runLaunchPerIterationLM(preArg))) return true;
             } else {
                 if (distributed ? trySlabOnChip(preArg) : tryOnChip(preArg, nullptr)) return true;
-                if ((!distributed || E->slabIterationAvailable()) && runLaunchPerIterationGN(preArg)) return true;
+                if ((!distributed || E->iterTraits(false).slabAvailable) && runLaunchPerIterationGN(preArg)) return true;
             }
         }
         if (redo) return false;

@@ -23,6 +23,7 @@
 //               __device__ MVec<T, C> apply(pc, pl, pr, pu, pd, hasL, hasR, hasU, hasD, coef) const; }     // (J^T J p) at an active pixel; p of an inactive / absent pixel is 0
 #pragma once
 #include "iw_device.h"
+#include "pcg_ring.h"
 
 namespace optamd {
 namespace {
@@ -236,21 +237,12 @@ __global__ __launch_bounds__(kBlk) void march_pcgIter(Op op, MarchK<T> K, int ro
     if (threadIdx.x == 0) { K.aDen[blockIdx.x] = v[0]; K.aNum[blockIdx.x] = v[1]; K.s2[blockIdx.x] = v[2]; K.s3[blockIdx.x] = v[3]; }
 }
 
-// delta += alpha p for the term an odd last launch still owes (alpha as that launch left it)
-template <class T>
-__global__ __launch_bounds__(kBlock) void march_axpyDeferred(T* __restrict__ delta, const T* __restrict__ p, const T* __restrict__ alpha, long n) {
-    const T a = alpha[0];
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) delta[i] += a * p[i];
-}
-
-// Host side of the loop: the ring of three p buffers, the alpha / beta slots, sweep direction and the deferred delta term (the bookkeeping of
-// ImageWarpingOps::pcgIteration, energy_image_warping.hip).
+// Host side of the loop: block size, grid shape and the kernel's argument block; which p buffer and alpha / beta slot a launch uses is the ring's business (pcg_ring.h).
 template <class T>
 struct MarchLoop {
-    T* ring[3] = {nullptr, nullptr, nullptr}; const T* r0Ptr = nullptr; T* alphaSlots = nullptr;
-    int iterIndex = 0, flip = 0, occ = 0, forceRows = 0, forceBlock = 0; bool deferredTerm = false;
+    PcgRing<T> ring;
+    int occ = 0, forceRows = 0, forceBlock = 0;
     MarchLoop() { if (const char* e = getenv("OPT_AMD_ITER_ROWS")) forceRows = atoi(e); forceBlock = devSwitch("OPT_AMD_MARCH_BLOCK", forceBlock); }
-    ~MarchLoop() { for (T* b : ring) if (b) (void)hipFree(b); if (alphaSlots) (void)hipFree(alphaSlots); }
     template <class Op>
     bool launch(const Op& op, int W, int H, const uint8_t* flags, int cus, const PcgIterArgs<T>& a, LaunchCtx& ctx, const T* coef = nullptr) {
         // 16-byte pixels leave room for 3 waves per SIMD in 768-thread workgroups (12 column strips side by side: fewer, fatter workgroups and a quarter of the partial
@@ -266,24 +258,16 @@ struct MarchLoop {
     bool launchB(const Op& op, int W, int H, const uint8_t* flags, int cus, const PcgIterArgs<T>& a, LaunchCtx& ctx, const T* coef) {
         constexpr int C = Op::C;
         if ((unsigned long long)W * H * C * sizeof(T) >= (1ull << 32)) return false;      // 32-bit buffer offsets
-        const size_t bytes = ((size_t)W * H * C + 3) / 4 * 4 * sizeof(T);                 // padded like the solver's vectors: its flat kernels read whole 16-byte packs of the last p
-        for (int j = 0; j < 3; ++j) if (!ring[j]) { HIP_CHECK(hipMalloc((void**)&ring[j], bytes)); HIP_CHECK(hipMemsetAsync(ring[j], 0, bytes, ctx.stream)); }
-        if (!alphaSlots) { HIP_CHECK(hipMalloc((void**)&alphaSlots, 4 * sizeof(T))); HIP_CHECK(hipMemsetAsync(alphaSlots, 0, 4 * sizeof(T), ctx.stream)); }   // [0,1] alpha, [2,3] beta, ping-pong
-        if (a.first) { iterIndex = 0; flip = 0; r0Ptr = a.rOld; }      // the solver swaps its r buffers after every launch; this one keeps r_0 until launch 1 has read it
+        ring.allocate((size_t)W * H * C, ctx.stream);
         if (occ == 0) {
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, march_pcgIter<T, Op, false, blk>, blk, 0));
             occ = std::max(1, std::min(occ, 8));
         }
-        const int k = iterIndex;
+        const typename PcgRing<T>::Launch L = ring.next(a.first != 0, false, a.rOld, a.pOld);      // (Gauss-Newton only: the loop is never restarted)
         MarchK<T> K{};
-        K.W = W; K.H = H; K.flags = flags; K.coef = coef; K.iter = k;
-        K.pOld = k == 0 ? a.pOld : ring[(k - 1) % 3];
-        K.qOld = k <= 1 ? r0Ptr : ring[(k - 2) % 3];
-        K.pNew = ring[k % 3]; K.delta = a.delta;
-        K.rfree = k <= 1 ? 2 : 1;
-        K.deltaMode = (k >= 2 && k % 2 == 0) ? 1 : 2;           // launch 0 has nothing to apply; odd launches defer
-        K.alphaOut = alphaSlots + (k & 1); K.alphaIn = alphaSlots + ((k & 1) ^ 1);
-        deferredTerm = k >= 1 && k % 2 == 1;                    // after an odd launch alpha_{k-1} p_{k-1} is still owed (finish)
+        K.W = W; K.H = H; K.flags = flags; K.coef = coef; K.iter = L.k;
+        K.pOld = L.pOld; K.qOld = L.rOld; K.pNew = L.pNew; K.delta = a.delta;
+        K.rfree = L.rfree; K.deltaMode = L.deltaMode; K.alphaOut = L.alphaOut; K.alphaIn = L.alphaIn;
         K.aNumPrev = a.aNumPrev.partials; K.aDenPrev = a.aDenPrev.partials; K.s2Prev = a.s2Prev.partials; K.s3Prev = a.s3Prev.partials;
         K.nNum = a.aNumPrev.n; K.nDen = a.aDenPrev.n; K.n2 = a.s2Prev.n; K.n3 = a.s3Prev.n;
         K.aNum = a.aNum->partials; K.aDen = a.aDen->partials; K.s2 = a.s2->partials; K.s3 = a.s3->partials;
@@ -295,25 +279,15 @@ struct MarchLoop {
         gy = divUp(H, rowsPerGroup);
         {
             ScopedKernel sk(ctx, "PCGIteration");
-            if (flip) march_pcgIter<T, Op, true, blk><<<gx * gy, blk, 0, ctx.stream>>>(op, K, rowsPerGroup, gx);
+            if (L.flip) march_pcgIter<T, Op, true, blk><<<gx * gy, blk, 0, ctx.stream>>>(op, K, rowsPerGroup, gx);
             else march_pcgIter<T, Op, false, blk><<<gx * gy, blk, 0, ctx.stream>>>(op, K, rowsPerGroup, gx);
         }
-        flip ^= 1;      // successive launches sweep top-down / bottom-up
-        ++iterIndex;
         a.aNum->n = a.aDen->n = a.s2->n = a.s3->n = gx * gy;
         return true;
     }
     // After the last launch L-1 of a linear solve: the deferred term alpha_{L-2} p_{L-2} of an odd last launch; returns where p_{L-1} lives (the solver adds alpha_{L-1} p_{L-1})
     const T* finish(T* delta, long n, int cus, LaunchCtx& ctx) {
-        if (iterIndex < 1) return nullptr;
-        const T* pLast = ring[(iterIndex - 1) % 3];
-        if (deferredTerm && iterIndex >= 2) {
-            ScopedKernel sk(ctx, "PCGStep2_delta");
-            const int g = (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, (long)cus * 8));
-            march_axpyDeferred<T><<<g, kBlock, 0, ctx.stream>>>(delta, ring[(iterIndex - 2) % 3], alphaSlots + ((iterIndex - 1) & 1), n);
-        }
-        deferredTerm = false;
-        return pLast;
+        return ring.finish(delta, n, (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, (long)cus * 8)), ctx);
     }
 };
 

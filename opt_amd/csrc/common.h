@@ -324,6 +324,9 @@ struct ScopedKernel {   // brackets one (logical) kernel launch with timing even
 };
 
 inline int divUp(long a, long b) { return (int)((a + b - 1) / b); }
+// Grid of a flat (grid-stride) kernel over n elements: the workgroups that cover them, at most 8 per CU and at most `cap` (kMaxPartials where every workgroup
+// leaves a partial sum: their number decides the order of the sum)
+inline int flatGrid(long n, int cus, long cap) { return (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, std::min<long>(cap, (long)cus * 8))); }
 
 __device__ __forceinline__ void sincosT(float a, float* s, float* c) { sincosf(a, s, c); }
 __device__ __forceinline__ void sincosT(double a, double* s, double* c) { sincos(a, s, c); }

@@ -172,20 +172,12 @@ struct EnergyOps {
     // Optional: one WHOLE Gauss-Newton PCG iteration as a single kernel (see PcgIterArgs and solver.hip).
     virtual bool pcgIteration(const PcgIterArgs<T>& /*args*/, LaunchCtx&) { return false; }
     // Optional (single GPU; Gauss-Newton also on row slabs): the WHOLE linear solve -- lIterations PCG iterations (solverGPUGaussNewton.t:1056-1092) from r = r_0, p = M r_0 as PCGInit1
-    // left them, then PCGLinearUpdate X += delta -- as one persistent launch that keeps the loop state on chip (iw_onchip.h).  r0 and p0 are only read; delta
+    // left them, then PCGLinearUpdate X += delta, guarded by the launch's failure word (iw_applyDelta, onchip_sync.h ocApplyDelta) -- as one persistent launch that keeps the loop state on chip (iw_onchip.h).  r0 and p0 are only read; delta
     // receives sum alpha_k p_k; traceDev (or nullptr) receives alphaNum, alphaDen, s2, s3 of every iteration (4 doubles each; beta numerator by expansion as
     // in PcgIterArgs).  false: the problem does not fit the chip or the kernel set has no such kernel -- nothing was touched.
     // lm != nullptr: the Levenberg-Marquardt loop instead (A = J^T J + diag(CtC), the q early-out decided on chip, the split residual reset as a second stencil pass;
     // r0 = b and p0 as PCGFinalizeDiagonal left them).  Then the kernel only produces delta: the solver applies savePreviousUnknowns + PCGLinearUpdate itself.
     virtual bool pcgSolveOnChip(const T* /*r0*/, const T* /*p0*/, T* /*delta*/, int /*lIterations*/, double* /*traceDev*/, const OnChipLm<T>* /*lm*/, LaunchCtx&) { return false; }
-    // an energy that does not precondition (UsePreconditioner(false): no preconditioner vector exists) but offers pcgSolveOnChip all the same
-    virtual bool onChipWithoutPreconditioner() const { return false; }
-    // Gauss-Newton: did pcgSolveOnChip end with PCGLinearUpdate (X += delta) itself?  false: the solver applies delta as after any other linear solve
-    virtual bool onChipAppliedUpdate() const { return true; }
-    // ... and if it did not: PCGLinearUpdate X += delta applied by the kernel set itself, GUARDED by the launch's failure word (a workgroup that gave up in the last wait only
-    // raises the flag while the others have already written their delta: an unguarded update would add a partial delta that Gauss-Newton -- no saved unknowns -- cannot take
-    // back).  false: no such kernel, the solver applies delta itself (Levenberg-Marquardt restores the saved unknowns on a failure).
-    virtual bool onChipGuardedUpdate(const T* /*delta*/, LaunchCtx&) { return false; }
     // Row slabs: would pcgSolveOnChip run for this rank's slab right now (kernel variant fits, unit lattice, the communicator offers onChipPlan ...)?  The solver
     // makes the decision collective (all ranks or none) before anyone launches.  onChipPlan / onChipCtx: the communicator's entry (OptAmd_SlabCommExt), set by the solver.
     virtual bool slabOnChipAvailable(int /*lIterations*/) { return false; }

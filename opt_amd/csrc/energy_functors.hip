@@ -214,34 +214,10 @@ __global__ __launch_bounds__(kBlock) void flow_coef(OpticalFlowE<T> e, T* __rest
     }
 }
 template <class T>
-struct OpticalFlowOps : StencilOps<T, OpticalFlowE<T>> {
-    MarchLoop<T> march; T* coef = nullptr; bool useMarch = true;
-    OpticalFlowOps(const unsigned* dims) : StencilOps<T, OpticalFlowE<T>>(dims, false) { if (const char* e = getenv("OPT_AMD_FLOW_MARCH")) useMarch = atoi(e) != 0; if (useMarch) oc.template reserveFor<FlowMarchOp<T>>(this->e.W, this->e.H, this->cus); }
-    ~OpticalFlowOps() override { if (coef) (void)hipFree(coef); }
-    bool deltaMovable() const override { return useMarch && !this->slab.active; }      // (PcgSolver::deltaTrial)
-    bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
-        if (!useMarch || a.pre || a.CtC) return false;      // Gauss-Newton only
-        const long n = (long)this->e.W * this->e.H;
-        if (!coef) HIP_CHECK(hipMalloc((void**)&coef, (size_t)(2 * n) * sizeof(T)));
-        if (a.first) { ScopedKernel k(ctx, "operatorCoefficients"); flow_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e, coef); }
-        return march.launch(FlowMarchOp<T>{this->e.w_fit, this->e.w_reg}, this->e.W, this->e.H, nullptr, this->cus, a, ctx, coef);
-    }
-    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, 2L * this->e.W * this->e.H, this->cus, ctx); }
-    // ---- the whole Gauss-Newton linear solve on chip (stencil_onchip.h); the operator's per-pixel coefficient is formed first, as for the marching loop ----
-    OnchipMarch<T> oc;
-    bool onChipWithoutPreconditioner() const override { return true; }
-    bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
-        if (!useMarch || traceDev || this->slab.active) return false;
-        int sx, ty, G;
-        if (!oc.guard.usable() || (lm && (!lm->CtC || lm->resetPeriod < L)) ||
-            !(lm ? oc.template select<FlowMarchOp<T>, true>(this->e.W, this->e.H, this->cus, sx, ty, G) : oc.template select<FlowMarchOp<T>, false>(this->e.W, this->e.H, this->cus, sx, ty, G))) return false;      // (before the coefficient pass is spent)
-        const long n = (long)this->e.W * this->e.H;
-        if (!coef) HIP_CHECK(hipMalloc((void**)&coef, (size_t)(2 * n) * sizeof(T)));
-        { ScopedKernel k(ctx, "operatorCoefficients"); flow_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e, coef); }
-        return oc.solve(FlowMarchOp<T>{this->e.w_fit, this->e.w_reg}, this->e.W, this->e.H, nullptr, coef, r0, p0, delta, const_cast<T*>(this->e.X[0]), L, this->cus, ctx, lm);
-    }
-    OnchipGuard* onChipGuard() override { return &oc.guard; }
-    std::string describe(int L, bool lmv) override { return oc.template describe<FlowMarchOp<T>>(this->e.W, this->e.H, this->cus, useMarch ? L : 0, lmv, "march_pcgIter"); }
+struct OpticalFlowOps : MarchOps<T, FlowMarchOp<T>, StencilOps<T, OpticalFlowE<T>>> {
+    OpticalFlowOps(const unsigned* dims) : MarchOps<T, FlowMarchOp<T>, StencilOps<T, OpticalFlowE<T>>>(dims, false) { this->marchInit(this->e.W, this->e.H, this->cus, "OPT_AMD_FLOW_MARCH", false, this->cus * 8L); }
+    FlowMarchOp<T> marchOp() const override { return {this->e.w_fit, this->e.w_reg}; }
+    void marchCoefficients(T* g, LaunchCtx& ctx) override { flow_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e, g); }
 };
 template <class T> EnergyOps<T>* makeFlow(const unsigned* dims) { return new OpticalFlowOps<T>(dims); }
 // ---- intrinsic_image_decomposition's Gauss-Newton PCG loop on the marching template ------------------------------------------------------------------------------
@@ -277,48 +253,11 @@ __global__ __launch_bounds__(kBlock) void intrinsic_coef(const T* __restrict__ a
     }
 }
 template <class T>
-struct IntrinsicOps : StencilOps<T, IntrinsicE<T>> {
-    MarchLoop<T> march; T* coef = nullptr; bool useMarch = true;
-    IntrinsicOps(const unsigned* dims) : StencilOps<T, IntrinsicE<T>>(dims, false) { if (const char* e = getenv("OPT_AMD_INTRINSIC_MARCH")) useMarch = atoi(e) != 0; if (useMarch) oc.template reserveFor<IntrinsicMarchOp<T>>(this->e.W, this->e.H, this->cus); }
-    ~IntrinsicOps() override { if (coef) (void)hipFree(coef); }
-    bool deltaMovable() const override { return useMarch && !this->slab.active; }      // (PcgSolver::deltaTrial)
-    bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
-        if (!useMarch || a.pre || a.CtC) return false;      // Gauss-Newton only
-        const long n = (long)this->e.W * this->e.H;
-        if (!coef) HIP_CHECK(hipMalloc((void**)&coef, (size_t)(4 * n) * sizeof(T)));
-        if (a.first) { ScopedKernel k(ctx, "operatorCoefficients"); intrinsic_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e.aux, coef, n); }
-        return march.launch(IntrinsicMarchOp<T>{this->e.w_fit, this->e.w_regA, this->e.w_regS}, this->e.W, this->e.H, nullptr, this->cus, a, ctx, coef);
-    }
-    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, 4L * this->e.W * this->e.H, this->cus, ctx); }
-    // ---- the whole linear solve on chip (stencil_onchip.h); the operator's coefficients are repacked first, as for the marching loop ----
-    OnchipMarch<T> oc;
-    bool onChipWithoutPreconditioner() const override { return true; }
-    bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
-        if (!useMarch || traceDev || this->slab.active) return false;
-        using Op = IntrinsicMarchOp<T>;
-        int sx, ty, G;
-        if (!oc.guard.usable() || (lm && (!lm->CtC || lm->resetPeriod < L)) ||
-            !(lm ? oc.template select<Op, true>(this->e.W, this->e.H, this->cus, sx, ty, G) : oc.template select<Op, false>(this->e.W, this->e.H, this->cus, sx, ty, G))) return false;
-        const long n = (long)this->e.W * this->e.H;
-        if (!coef) HIP_CHECK(hipMalloc((void**)&coef, (size_t)(4 * n) * sizeof(T)));
-        { ScopedKernel k(ctx, "operatorCoefficients"); intrinsic_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e.aux, coef, n); }
-        // (X += delta runs flat over the solver's layout: the two unknown images are consecutive there, but the CALLER's two arrays need not be -- the update stays with the solver)
-        return oc.solve(Op{this->e.w_fit, this->e.w_regA, this->e.w_regS}, this->e.W, this->e.H, nullptr, coef, r0, p0, delta, (T*)nullptr, L, this->cus, ctx, lm);
-    }
-    bool onChipAppliedUpdate() const override { return false; }
-    bool onChipGuardedUpdate(const T* delta, LaunchCtx& ctx) override {      // X += delta per unknown image, unless the launch raised its failure word
-        if (!oc.guard.bad || !oc.guard.launched) return false;
-        ScopedKernel k(ctx, "PCGLinearUpdate");
-        for (size_t i = 0; i < this->unknowns.size(); ++i) {
-            const auto& u = this->unknowns[i];
-            const long cnt = u.elems * u.channels;
-            const int grid = (int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, 4096));
-            march_applyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(this->unknownPtr((int)i), delta + u.offset, cnt, oc.guard.bad, oc.guard.hostErr);
-        }
-        return true;
-    }
-    OnchipGuard* onChipGuard() override { return &oc.guard; }
-    std::string describe(int L, bool lmv) override { return oc.template describe<IntrinsicMarchOp<T>>(this->e.W, this->e.H, this->cus, useMarch ? L : 0, lmv, "march_pcgIter"); }
+struct IntrinsicOps : MarchOps<T, IntrinsicMarchOp<T>, StencilOps<T, IntrinsicE<T>>> {
+    // (the guarded X += delta runs per unknown image: the two images are consecutive in the solver's layout, but the CALLER's two arrays need not be)
+    IntrinsicOps(const unsigned* dims) : MarchOps<T, IntrinsicMarchOp<T>, StencilOps<T, IntrinsicE<T>>>(dims, false) { this->marchInit(this->e.W, this->e.H, this->cus, "OPT_AMD_INTRINSIC_MARCH", false, 4096); }
+    IntrinsicMarchOp<T> marchOp() const override { return {this->e.w_fit, this->e.w_regA, this->e.w_regS}; }
+    void marchCoefficients(T* coef, LaunchCtx& ctx) override { intrinsic_coef<T><<<this->grid(), kBlock, 0, ctx.stream>>>(this->e.aux, coef, (long)this->e.W * this->e.H); }
 };
 template <class T> EnergyOps<T>* makeIntrinsic(const unsigned* dims) { return new IntrinsicOps<T>(dims); }
 // OPT_AMD_VOLUMETRIC_ARAP=0: the functor engine; default: ARAP's kernel set on the lattice graph (graph_common.h makeVolumetricOnArap -- the same energy, 151 -> ... ms at 96^3)

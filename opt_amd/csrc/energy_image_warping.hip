@@ -60,7 +60,7 @@ struct ImageWarpingOps : EnergyOps<T> {
         (void)hipFree(A.flags); (void)hipFree(A.cs); (void)hipFree(dNotLattice);
         if (lmQState) (void)hipFree(lmQState);
     }
-    int flatGrid(long n) const { return (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, std::min<long>(kMaxPartials, (long)cus * 8))); }
+    int flatGrid(long n) const { return optamd::flatGrid(n, cus, kMaxPartials); }
 
     // ---- bind: flag bytes + is UrShape the unit lattice? (the reference example always passes the pixel grid, CombinedSolver.h:161-172) ---------------------
     int* hNotLattice = nullptr; int* dNotLattice = nullptr; hipEvent_t bindEvent = nullptr; bool verdictPending = false, lattice = false;

@@ -256,25 +256,24 @@ __global__ __launch_bounds__(PS * PS) void poisson_patchSolve(int W, int H, cons
 }
 
 template <class T>
-struct PoissonOps : EnergyOps<T> {
+struct PoissonOps : MarchOps<T, PoissonMarchOp<T>, EnergyOps<T>> {
     PArgs<T> A{};
     int cus = 256;
-    bool singleKernel = true;
-    MarchLoop<T> march; uint8_t* flags = nullptr;      // bit 0: M == 0 (the pixel is an unknown), refreshed at every bind
+    uint8_t* flags = nullptr;      // bit 0: M == 0 (the pixel is an unknown), refreshed at every bind
     PoissonOps(const unsigned* dims) {
         A.W = (int)dims[0]; A.H = (int)dims[1];
         this->usePreconditioner = false;                       // poisson_image_editing.t:5
         this->addUnknown(0, (long)A.W * A.H, 4);
         int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (const char* e = getenv("OPT_AMD_POISSON_ONEKERNEL")) singleKernel = atoi(e) != 0;
-        if (singleKernel) oc.template reserveFor<PoissonMarchOp<T>>(A.W, A.H, cus);
+        this->marchInit(A.W, A.H, cus, "OPT_AMD_POISSON_ONEKERNEL", true, cus * 8L);
     }
-    int grid() const { return (int)std::max<long>(1, std::min<long>(((long)A.W * A.H + kBlock - 1) / kBlock, std::min<long>(kMaxPartials, (long)cus * 8))); }
+    PoissonMarchOp<T> marchOp() const override { return {}; }
+    int grid() const { return flatGrid((long)A.W * A.H, cus, kMaxPartials); }
     void bind(void** p, LaunchCtx& ctx) override {
         A.X = (const T*)p[0]; A.Tg = (const T*)p[1]; A.M = (const T*)p[2];
-        if (singleKernel) {
+        if (this->useMarch) {
             const long n = (long)A.W * A.H;
-            if (!flags) HIP_CHECK(hipMalloc((void**)&flags, (size_t)n));
+            if (!flags) { HIP_CHECK(hipMalloc((void**)&flags, (size_t)n)); this->marchFlags = flags; }
             poisson_flags<T><<<grid(), kBlock, 0, ctx.stream>>>(A.M, flags, n);
         }
     }
@@ -290,21 +289,6 @@ struct PoissonOps : EnergyOps<T> {
     void evalModelCost(const T* delta, Reduction& out, LaunchCtx& ctx) override {
         ScopedKernel k(ctx, "computeModelCost"); poisson_cost<T, 1><<<grid(), kBlock, 0, ctx.stream>>>(A, delta, out.partials); out.n = grid();
     }
-    bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
-        if (!singleKernel || a.pre || a.CtC) return false;      // Gauss-Newton only: the Levenberg-Marquardt loop keeps the generic kernels
-        return march.launch(PoissonMarchOp<T>{}, A.W, A.H, flags, cus, a, ctx);
-    }
-    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, 4L * A.W * A.H, cus, ctx); }
-    bool deltaMovable() const override { return !this->slab.active; }      // (the march takes delta from its arguments at every launch: PcgSolver::deltaTrial)
-    // ---- the whole Gauss-Newton linear solve on chip (stencil_onchip.h) ----
-    OnchipMarch<T> oc;
-    bool onChipWithoutPreconditioner() const override { return true; }
-    bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
-        if (!singleKernel || traceDev || this->slab.active) return false;
-        return oc.solve(PoissonMarchOp<T>{}, A.W, A.H, flags, nullptr, r0, p0, delta, const_cast<T*>(A.X), L, cus, ctx, lm);
-    }
-    OnchipGuard* onChipGuard() override { return &oc.guard; }
-    std::string describe(int L, bool lmv) override { return oc.template describe<PoissonMarchOp<T>>(A.W, A.H, cus, singleKernel ? L : 0, lmv, "march_pcgIter"); }
     // ---- patch solver: ping-pong between the caller's X and a scratch copy; patchFinish leaves the result in the caller's buffer
     T* scratchX = nullptr; bool inScratch = false;
     bool supportsPatch() const override { return true; }
@@ -382,7 +366,7 @@ __global__ __launch_bounds__(kBlock) void lap_applyJTJ(LArgs A, const float* __r
     if (threadIdx.x == 0 && partials) partials[blockIdx.x] = t;
 }
 
-struct LaplacianOps : EnergyOps<float> {
+struct LaplacianOps : MarchOps<float, LaplacianMarchOp, EnergyOps<float>> {
     LArgs A{};
     int cus = 256;
     LaplacianOps(const unsigned* dims) {
@@ -390,9 +374,10 @@ struct LaplacianOps : EnergyOps<float> {
         this->usePreconditioner = false;                       // no UsePreconditioner call in laplacian.t (default o.t:214)
         this->addUnknown(0, (long)A.W * A.H, 1);
         int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        oc.template reserveFor<LaplacianMarchOp>(A.W, A.H, cus);
+        this->marchInit(A.W, A.H, cus, nullptr, true, cus * 8L);
     }
-    int grid() const { return (int)std::max<long>(1, std::min<long>(((long)A.W * A.H + kBlock - 1) / kBlock, std::min<long>(kMaxPartials, (long)cus * 8))); }
+    LaplacianMarchOp marchOp() const override { return {}; }
+    int grid() const { return flatGrid((long)A.W * A.H, cus, kMaxPartials); }
     void bind(void** p, LaunchCtx&) override { A.X = (const float*)p[0]; A.Aim = (const float*)p[1]; }
     float* unknownPtr(int) const override { return const_cast<float*>(A.X); }
     void evalCost(Reduction& out, LaunchCtx& ctx) override { ScopedKernel k(ctx, "computeCost"); lap_cost<0><<<grid(), kBlock, 0, ctx.stream>>>(A, nullptr, out.partials); out.n = grid(); }
@@ -406,21 +391,6 @@ struct LaplacianOps : EnergyOps<float> {
     void evalModelCost(const float* delta, Reduction& out, LaunchCtx& ctx) override {
         ScopedKernel k(ctx, "computeModelCost"); lap_cost<1><<<grid(), kBlock, 0, ctx.stream>>>(A, delta, out.partials); out.n = grid();
     }
-    MarchLoop<float> march;
-    bool pcgIteration(const PcgIterArgs<float>& a, LaunchCtx& ctx) override {
-        if (a.pre || a.CtC) return false;
-        return march.launch(LaplacianMarchOp{}, A.W, A.H, nullptr, cus, a, ctx);
-    }
-    const float* pcgFinish(float* delta, LaunchCtx& ctx) override { return march.finish(delta, (long)A.W * A.H, cus, ctx); }
-    bool deltaMovable() const override { return !this->slab.active; }
-    OnchipMarch<float> oc;      // the whole Gauss-Newton linear solve on chip (stencil_onchip.h)
-    bool onChipWithoutPreconditioner() const override { return true; }
-    bool pcgSolveOnChip(const float* r0, const float* p0, float* delta, int L, double* traceDev, const OnChipLm<float>* lm, LaunchCtx& ctx) override {
-        if (traceDev || this->slab.active) return false;
-        return oc.solve(LaplacianMarchOp{}, A.W, A.H, nullptr, nullptr, r0, p0, delta, const_cast<float*>(A.X), L, cus, ctx, lm);
-    }
-    OnchipGuard* onChipGuard() override { return &oc.guard; }
-    std::string describe(int L, bool lmv) override { return oc.describe<LaplacianMarchOp>(A.W, A.H, cus, L, lmv, "march_pcgIter"); }
 };
 
 template <class T> EnergyOps<T>* makePoisson(const unsigned* dims) { return new PoissonOps<T>(dims); }

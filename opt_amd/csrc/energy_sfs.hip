@@ -636,10 +636,18 @@ struct SfsOps : EnergyOps<T> {
         if (const char* e = getenv("OPT_AMD_SFS_ONEKERNEL")) oneKernel = atoi(e) != 0;
         gridOverride = devSwitch("OPT_AMD_SFS_GRID", gridOverride);
         if (const char* e = getenv("OPT_AMD_SFS_MARCH_GRID")) marchGridOverride = atoi(e);
-        soReserve();
+        // Which variant, if any: among those whose workgroups fit one per CU, the one with the fewest marching trips per SIMD and iteration -- (waves per SIMD) x (rows
+        // held per wave).  The buffers are sized for the plan's image when the plan is made.
+        oc.init(OcFamily{kSoSpan, 4, kSoMaxG, kSoNW, "sfs_onchipPcg", "sfs_pcgMarch", "sfs_pcgMarch",
+                         "Opt(amd): the on-chip shape_from_shading kernel (%d rows, %d waves) could not be launched; the plan stays on the marching kernels\n"},
+                soVariantList, A.W, A.H, 1, cus, std::min<long>(kMaxPartials, cus * 8L));
+        oc.reserve();
+#if SO_PROFILE
+        if (oc.slots && getenv("OPT_AMD_ONCHIP_PROFILE")) { HIP_CHECK(hipMalloc((void**)&soProf, sizeof(long long) * 8 * kSoMaxG)); owned.push_back(soProf); }
+#endif
     }
     ~SfsOps() override { for (void* p : owned) (void)hipFree(p); }
-    int grid() const { return (int)std::max<long>(1, std::min<long>(((long)A.W * A.H + kBlock - 1) / kBlock, std::min<long>(kMaxPartials, (long)cus * 8))); }
+    int grid() const { return flatGrid((long)A.W * A.H, cus, kMaxPartials); }
     void bind(void** p, LaunchCtx&) override {
         // sqrt(Param(...)) is evaluated in opt_float on the float parameter (shape_from_shading.t:4-6)
         A.w_p = std::sqrt((T) * (const float*)p[0]); A.w_s = std::sqrt((T) * (const float*)p[1]); A.w_g = std::sqrt((T) * (const float*)p[2]);
@@ -746,16 +754,14 @@ struct SfsOps : EnergyOps<T> {
         return true;
     }
 
-    // ---- the whole linear solve on chip (sfs_onchip.h): Gauss-Newton or Levenberg-Marquardt, one GPU, workgroups <= CUs ---------------------------------------------
+    // ---- the whole linear solve on chip (sfs_onchip.h; host side: onchip_launch.h): Gauss-Newton or Levenberg-Marquardt, one GPU, workgroups <= CUs ------------------
     // OPT_AMD_ONCHIP* (onchip_sync.h OnchipGuard): ROWS=r / WAVES=w force the variant that owns r rows per wave / has w waves per workgroup.
-    struct SoVariant { int rows, waves; const void* gn; const void* lm; };
-    OnchipGuard guard;
-    OnchipGuard* onChipGuard() override { return &guard; }
+    OnchipLauncher<T> oc;
+    OnchipGuard* onChipGuard() override { return &oc.guard; }
     long long* soProf = nullptr;
-    oc_u64 *soSlots = nullptr, *soBox = nullptr;      // the tagged buffers
-    static const std::vector<SoVariant>& soVariants() {
-        static const std::vector<SoVariant> v = [] {
-            std::vector<SoVariant> o;
+    static const std::vector<OcVariant>& soVariantList() {
+        static const std::vector<OcVariant> v = [] {
+            std::vector<OcVariant> o;
 #define SO_VARIANT(R, WV) o.push_back({R, WV, (const void*)sfs_onchipPcg<T, R, false, WV>, (const void*)sfs_onchipPcg<T, R, true, WV>})
             SO_VARIANT(4, 4); SO_VARIANT(6, 4); SO_VARIANT(8, 4); SO_VARIANT(10, 4);
             SO_VARIANT(4, 8); SO_VARIANT(6, 8); SO_VARIANT(8, 8); SO_VARIANT(10, 8);
@@ -764,87 +770,34 @@ struct SfsOps : EnergyOps<T> {
         }();
         return v;
     }
-    // Which variant, if any: among those whose workgroups fit one per CU, the one with the fewest marching trips per SIMD and iteration -- (waves per SIMD) x (rows
-    // held per wave); ties go to the fewer rows (less work behind the wait).
-    const SoVariant* soSelect(int& stripsX, int& tilesY, int& G) const {
-        stripsX = divUp(A.W, kSoSpan);
-        const SoVariant* best = nullptr; int bestCost = 1 << 30;
-        for (const auto& v : soVariants()) {
-            if (guard.forceRows && v.rows != guard.forceRows) continue;
-            if (guard.forceWaves && v.waves != guard.forceWaves) continue;
-            const int ty = divUp(A.H, v.rows), g = divUp(stripsX * ty, v.waves);
-            if (g > std::min(cus, kSoMaxG)) continue;
-            const int cost = (v.waves == 4 ? 100 : 136) * (v.rows + 4);      // (measured: two waves per SIMD march a pair of trips in 1.36 of the time one wave marches one)
-            if (cost < bestCost) { best = &v; bestCost = cost; tilesY = ty; G = g; }
-        }
-        return best;
-    }
-    // the buffers of the path, sized for the plan's image when the plan is made (so that its first linear solve does not pay for the allocations)
-    void soReserve() {
-        if (soSlots || !guard.enabled || (unsigned long long)A.W * A.H * sizeof(T) >= (1ull << 30)) return;
-        { int sx, ty, g; if (!soSelect(sx, ty, g)) return; }      // (the image does not fit the chip: the path will never be taken)
-        soSlots = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)kSoMaxG * kSoNW);
-        soBox = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)A.W * A.H * (sizeof(T) / 4));
-        guard.allocWords(nullptr); guard.clearTagged(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr));      // (done before the plan's own stream sees the buffers)
-#if SO_PROFILE
-        if (getenv("OPT_AMD_ONCHIP_PROFILE")) { HIP_CHECK(hipMalloc((void**)&soProf, sizeof(long long) * 8 * kSoMaxG)); owned.push_back(soProf); }
-#endif
-    }
-    bool onChipWithoutPreconditioner() const override { return true; }
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lmArgs, LaunchCtx& ctx) override {
-        if (!guard.usable() || this->slab.active || traceDev || L <= 0 || (unsigned long long)A.W * A.H * sizeof(T) >= (1ull << 30)) return false;
-        if (lmArgs && (!lmArgs->CtC || lmArgs->resetPeriod < L)) return false;      // a split residual reset before the last iteration: the marching loop's business
-        int stripsX = 0, tilesY = 0, G = 0;
-        const SoVariant* V = soSelect(stripsX, tilesY, G);
-        if (!V) return false;
-        if (!soSlots) { soReserve(); if (!soSlots) return false; }
-        const unsigned tag0 = guard.tags((unsigned)L, ctx.stream);
-        const OcTimeouts tmo = guard.timeouts(L, false);
-        SfsOcArgs<T> K{A, r0, p0, lmArgs ? lmArgs->CtC : nullptr, delta, stripsX, tilesY, G, L, tag0, soSlots, soBox, guard.bad, tmo.later, guard.failAtThisLaunch(), tmo.first, lmArgs ? lmArgs->qTolerance : T(0),
-                       lmArgs ? guard.hostErr : nullptr, soProf, lmArgs ? lmArgs->breakInfo : nullptr};
-        {
-            ScopedKernel k(ctx, "PCGSolveOnChip");
+        if (this->slab.active || traceDev) return false;
+        return oc.solve(L, lmArgs, delta, *this, ctx, [&](const OcGrant& g) {
+            SfsOcArgs<T> K{A, r0, p0, lmArgs ? lmArgs->CtC : nullptr, delta, g.stripsX, g.tilesY, g.G, L, g.tag0, g.slots, g.box, g.bad, g.tmo.later, g.failAt, g.tmo.first, lmArgs ? lmArgs->qTolerance : T(0),
+                           g.hostErr, soProf, lmArgs ? lmArgs->breakInfo : nullptr};
             void* kargs[] = {(void*)&K};
-            if (hipLaunchKernel(lmArgs ? V->lm : V->gn, dim3(G), dim3(V->waves * kWave), kargs, 0, ctx.stream) != hipSuccess) {      // (a device that cannot hold the variant's LDS: not offered again)
-                (void)hipGetLastError(); guard.enabled = false;
-                fprintf(stderr, "Opt(amd): the on-chip shape_from_shading kernel (%d rows, %d waves) could not be launched; the plan stays on the marching kernels\n", V->rows, V->waves);
-                return false;
-            }
-        }
+            if (!g.launch(kargs, ctx.stream)) return false;
 #if SO_PROFILE
-        if (soProf) {      // development builds: where an iteration's time goes (thread 0 of every workgroup; mean and max over the workgroups)
-            std::vector<long long> h((size_t)G * 8);
-            HIP_CHECK(hipStreamSynchronize(ctx.stream));
-            HIP_CHECK(hipMemcpy(h.data(), soProf, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            const char* names[6] = {"march", "wave-sums", "barrier", "wait", "grid-sum", "update"};
-            fprintf(stderr, "sfs on-chip profile %dx%d rows=%d waves=%d G=%d L=%d (us per iteration: mean / max over workgroups):", A.W, A.H, V->rows, V->waves, G, L);
-            for (int ph = 0; ph < 6; ++ph) {
-                double mean = 0, mx = 0;
-                for (int b = 0; b < G; ++b) { const double v = h[(size_t)b * 8 + ph] * 0.01 / L; mean += v / G; mx = std::max(mx, v); }
-                fprintf(stderr, "  %s %.2f / %.2f", names[ph], mean, mx);
+            if (soProf) {      // development builds: where an iteration's time goes (thread 0 of every workgroup; mean and max over the workgroups)
+                const int G = g.G;
+                std::vector<long long> h((size_t)G * 8);
+                HIP_CHECK(hipStreamSynchronize(ctx.stream));
+                HIP_CHECK(hipMemcpy(h.data(), soProf, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+                const char* names[6] = {"march", "wave-sums", "barrier", "wait", "grid-sum", "update"};
+                fprintf(stderr, "sfs on-chip profile %dx%d rows=%d waves=%d G=%d L=%d (us per iteration: mean / max over workgroups):", A.W, A.H, g.V->rows, g.V->waves, G, L);
+                for (int ph = 0; ph < 6; ++ph) {
+                    double mean = 0, mx = 0;
+                    for (int b = 0; b < G; ++b) { const double v = h[(size_t)b * 8 + ph] * 0.01 / L; mean += v / G; mx = std::max(mx, v); }
+                    fprintf(stderr, "  %s %.2f / %.2f", names[ph], mean, mx);
+                }
+                { double r6 = 0, r7 = 0; for (int b = 0; b < G; ++b) { r6 += (double)h[(size_t)b * 8 + 6] / L / G; r7 += h[(size_t)b * 8 + 7] * 0.01 / L / G; } fprintf(stderr, "  [thread 0: first round %.2f us, %.2f further rounds per iteration]", r7, r6); }
+                fprintf(stderr, "\n");
             }
-            { double r6 = 0, r7 = 0; for (int b = 0; b < G; ++b) { r6 += (double)h[(size_t)b * 8 + 6] / L / G; r7 += h[(size_t)b * 8 + 7] * 0.01 / L / G; } fprintf(stderr, "  [thread 0: first round %.2f us, %.2f further rounds per iteration]", r7, r6); }
-            fprintf(stderr, "\n");
-        }
 #endif
-        if (!lmArgs) {      // (LM: the solver applies the update itself; a workgroup that gave up has told the host on its way out)
-            ScopedKernel k(ctx, "PCGLinearUpdate");
-            const long N = (long)A.W * A.H;
-            sfs_applyDelta<T><<<grid(), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.X), delta, N, guard.bad, guard.hostErr);
-        }
-        guard.launched = true;
-        return true;
+            return true;
+        });
     }
-    std::string describe(int L, bool lmv) override {      // ("key=value; ..." -- no ';' inside a value)
-        int stripsX = 0, tilesY = 0, G = 0;
-        const SoVariant* V = (guard.usable() && !this->slab.active && L > 0) ? soSelect(stripsX, tilesY, G) : nullptr;
-        char buf[600];
-        if (V) snprintf(buf, sizeof buf, "path=on-chip (sfs_onchipPcg%s%s); onchip_rows_per_wave=%d; waves_per_workgroup=%d; wave_tiles=%dx%d of 60 x %d pixels; workgroups=%d of %d CUs; fallback=one launch per PCG iteration (sfs_pcgMarch)",
-                        lmv ? ", LM" : "", lmv ? " while lIterations <= residual_reset_period" : "", V->rows, V->waves, stripsX, tilesY, V->rows, G, cus);
-        else snprintf(buf, sizeof buf, "path=one launch per PCG iteration (sfs_pcgMarch%s); why_not_on_chip=%s", lmv ? ", LM" : "",
-                      guard.whyOff() ? guard.whyOff() : this->slab.active ? "row slabs" : "the wave tiles do not fit the CUs");
-        return buf;
-    }
+    std::string describe(int L, bool lmv) override { return oc.describe(L, lmv, this->slab.active ? "row slabs" : nullptr); }
 };
 
 template <class T> EnergyOps<T>* makeSfs(const unsigned* dims) { return new SfsOps<T>(dims); }

@@ -1,0 +1,110 @@
+// Host side of the wave-tiled on-chip linear solves -- stencil_onchip.h (5-point stencils, a one-pixel ring) and sfs_onchip.h (shape_from_shading, a two-pixel ring): the
+// time-out guard, the two tagged buffers, which variant (if any) a plan takes, the launch, the guarded X += delta behind a Gauss-Newton solve and describe()'s text.
+// The device kernels differ; what differs for the host is data (OcFamily, the variant list).  image_warping's on-chip solve (tiles, dynamic LDS, row slabs) has a
+// host side of its own (energy_image_warping.hip).
+#pragma once
+#include "energy.h"
+#include "onchip_sync.h"
+
+namespace optamd {
+namespace {
+
+struct OcVariant { int rows, waves; const void *gn, *lm; };      // rows a wave owns, waves per workgroup, the Gauss-Newton / Levenberg-Marquardt kernel (nullptr: not offered)
+struct OcFamily {
+    int span, halo, maxG, words;             // pixels a wave owns per row; rows it holds around its own (the cost model); workgroup cap; tagged words per workgroup
+    const char *kernel, *loopGN, *loopLM;    // describe(): the kernel, the launch-per-iteration loops it stands in for
+    const char* launchFailed;                // stderr text (rows, waves) when the launch itself is refused, or nullptr: silent
+};
+struct OcPlan {
+    const OcVariant* V = nullptr; int stripsX = 0, tilesY = 0, G = 0;
+    explicit operator bool() const { return V != nullptr; }
+};
+// What a family fills its kernel's argument struct from; launch() is the launch of the chosen variant.
+struct OcGrant : OcPlan {
+    const void* fn; unsigned tag0; oc_u64 *slots, *box; int* bad; OcTimeouts tmo; int failAt;
+    int* hostErr;      // LM (the solver applies the update itself): the pinned word a workgroup that gave up raises on its way out; Gauss-Newton: nullptr (ocApplyDelta tells the host)
+    bool launch(void** kargs, hipStream_t s) const { return hipLaunchKernel(fn, dim3(G), dim3(V->waves * kWave), kargs, 0, s) == hipSuccess; }
+};
+
+template <class T>
+struct OnchipLauncher {
+    OnchipGuard guard;      // the switches (OPT_AMD_ONCHIP*) and the time-out verdict
+    oc_u64 *slots = nullptr, *box = nullptr;      // the tagged buffers: [2][maxG][words] sums, [2][W * H * C * sizeof(T) / 4] ring
+    OcFamily fam{};
+    const std::vector<OcVariant>& (*variants)() = nullptr;
+    int W = 0, H = 0, C = 1, cus = 0;      // the plan's image (the dimensions of a plan are fixed), scalars per pixel
+    long updateCap = 0;                    // workgroups of the guarded update, per unknown image
+    void init(const OcFamily& f, const std::vector<OcVariant>& (*v)(), int W_, int H_, int C_, int cus_, long updateCap_) { fam = f; variants = v; W = W_; H = H_; C = C_; cus = cus_; updateCap = updateCap_; }
+    // among the variants whose workgroups fit one per CU: the least marching time per SIMD and iteration
+    OcPlan select(bool lm) const {
+        OcPlan best; int bestCost = 1 << 30;
+        const int stripsX = divUp(W, fam.span);
+        for (const auto& v : variants()) {
+            if (!(lm ? v.lm : v.gn)) continue;
+            if (guard.forceRows && v.rows != guard.forceRows) continue;
+            if (guard.forceWaves && v.waves != guard.forceWaves) continue;
+            const int ty = divUp(H, v.rows), g = divUp(stripsX * ty, v.waves);
+            if (g > std::min(cus, fam.maxG)) continue;
+            const int cost = (v.waves == 4 ? 100 : 136) * (v.rows + fam.halo);      // (measured: two waves per SIMD march a pair of trips in 1.36 of the time one wave marches one)
+            if (cost < bestCost) { best = OcPlan{&v, stripsX, ty, g}; bestCost = cost; }
+        }
+        return best;
+    }
+    // THE predicate: would a linear solve of L iterations run on chip, and with which variant?  lmv: the Levenberg-Marquardt loop (lm: its controls, where the caller has
+    // them -- a split residual reset before the last iteration is the launch-per-iteration loop's business).  solve(), describe(), reserve() and a kernel set that wants
+    // to know before it spends a coefficient pass all ask here.
+    OcPlan plan(int L, bool lmv, const OnChipLm<T>* lm = nullptr) const {
+        if (!guard.usable() || L <= 0 || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return {};
+        if (lm && (!lm->CtC || lm->resetPeriod < L)) return {};
+        return select(lmv);
+    }
+    // The buffers of the path, when the plan is made (so that its first linear solve does not pay for the allocations) -- only for plans that can take the path at all:
+    // some variant fits this device's CUs for the image (a 4-channel double image of 1-2 M pixels would otherwise hold ~256 MB of tagged box it could never use)
+    void reserve() {
+        if (slots || !(plan(1, false) || plan(1, true))) return;
+        slots = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)fam.maxG * fam.words);
+        box = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)W * H * C * (sizeof(T) / 4));
+        guard.allocWords(nullptr); guard.clearTagged(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr));      // (done before the plan's own stream sees the buffers)
+    }
+    // The whole linear solve and, behind a Gauss-Newton one, X += delta over the kernel set's unknown images; false (nothing touched): not offered for this plan.
+    // launchWith(grant): the family fills its kernel's arguments and calls grant.launch (false: the launch was refused -- the path is switched off).
+    template <class Fill>
+    bool solve(int L, const OnChipLm<T>* lm, const T* delta, const EnergyOps<T>& ops, LaunchCtx& ctx, Fill&& launchWith) {
+        const OcPlan P = plan(L, lm != nullptr, lm);
+        if (!P) return false;
+        if (!slots) { reserve(); if (!slots) return false; }
+        OcGrant g{P, lm ? P.V->lm : P.V->gn, guard.tags((unsigned)L, ctx.stream), slots, box, guard.bad, guard.timeouts(L, false), guard.failAtThisLaunch(), lm ? guard.hostErr : nullptr};
+        {
+            ScopedKernel k(ctx, "PCGSolveOnChip");
+            if (!launchWith(g)) {      // (a device that cannot hold the variant's LDS: not offered again)
+                (void)hipGetLastError(); guard.enabled = false;
+                if (fam.launchFailed) fprintf(stderr, fam.launchFailed, P.V->rows, P.V->waves);
+                return false;
+            }
+        }
+        if (!lm) {      // (LM: the solver applies the update itself)
+            ScopedKernel k(ctx, "PCGLinearUpdate");
+            for (size_t i = 0; i < ops.unknowns.size(); ++i) {
+                const auto& u = ops.unknowns[i];
+                const long cnt = u.elems * u.channels;
+                const int grid = (int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, updateCap));
+                ocApplyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(ops.unknownPtr((int)i), delta + u.offset, cnt, guard.bad, guard.hostErr);
+            }
+        }
+        guard.launched = true;
+        return true;
+    }
+    // ("key=value; ..." -- no ';' inside a value)  blocked: the kernel set's own reason to keep the plan off the chip, or nullptr
+    std::string describe(int L, bool lmv, const char* blocked = nullptr) const {
+        const OcPlan P = blocked ? OcPlan{} : plan(L, lmv);
+        char buf[600];
+        if (P) snprintf(buf, sizeof buf, "path=on-chip (%s%s); onchip_rows_per_wave=%d; waves_per_workgroup=%d; wave_tiles=%dx%d of %d x %d pixels; workgroups=%d of %d CUs; fallback=one launch per PCG iteration (%s)",
+                        fam.kernel, lmv ? ", LM while lIterations <= residual_reset_period" : "", P.V->rows, P.V->waves, P.stripsX, P.tilesY, fam.span, P.V->rows, P.G, cus, lmv ? fam.loopLM : fam.loopGN);
+        else snprintf(buf, sizeof buf, "path=one launch per PCG iteration (%s%s); why_not_on_chip=%s", lmv ? fam.loopLM : fam.loopGN, lmv ? ", LM" : "",
+                      guard.whyOff() ? guard.whyOff() : blocked ? blocked : "the wave tiles do not fit the CUs");
+        return buf;
+    }
+};
+
+}  // namespace
+}  // namespace optamd

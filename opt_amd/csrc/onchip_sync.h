@@ -1,4 +1,4 @@
-// Grid-wide hand-off primitives of the persistent ("on-chip") solver kernels: iw_onchip.h (image_warping), sfs_onchip.h, stencil_onchip.h.
+// Grid-wide hand-off primitives of the persistent ("on-chip") solver kernels: iw_onchip.h (image_warping), sfs_onchip.h, stencil_onchip.h (host side of the last two: onchip_launch.h).
 //
 // Everything that crosses workgroups inside such a kernel travels as naturally aligned 8-byte words {payload, tag}: ONE relaxed agent-scope store each (global_store sc1:
 // written through, no fence, no cache write-back) and relaxed agent-scope loads on the polling side (MI355X_MICROARCH.md "handoff-1to1" / granule "R2"; measured in
@@ -140,6 +140,16 @@ __device__ __forceinline__ double ocWaveSum63(double v) {
     v = ocDppAdd<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
     v = ocDppAdd<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3
     return v;
+}
+
+// PCGLinearUpdate X += delta (solver.t:552-557) behind an on-chip Gauss-Newton solve -- unless a wait timed out: then the unknowns stay untouched and the host is told
+template <class T>
+__global__ __launch_bounds__(kBlock) void ocApplyDelta(T* __restrict__ X, const T* __restrict__ delta, long n, const int* __restrict__ bad, int* hostErr) {
+    if (__hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(hostErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) X[i] = X[i] + delta[i];
 }
 
 }  // namespace

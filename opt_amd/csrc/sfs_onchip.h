@@ -1,6 +1,6 @@
 // shape_from_shading: the WHOLE PCG linear solve of one Gauss-Newton / Levenberg-Marquardt step as one persistent launch whose loop state never leaves the chip.
 //
-// Included by energy_sfs.hip behind the marching kernels (host side: SfsOps::pcgSolveOnChip).  What it replaces: the reference's loop
+// Included by energy_sfs.hip behind the marching kernels (host side: onchip_launch.h, SfsOps::pcgSolveOnChip).  What it replaces: the reference's loop
 // `for lIter = 0, lIterations do PCGStep1; PCGStep2; PCGStep3 end` (solverGPUGaussNewton.t:1056-1103) -- three launches and two same-address-atomic sums per
 // iteration there, one marching launch per iteration in sfs_pcgMarch -- for images whose loop state fits the register files (the reference's own input is
 // 640 x 480, examples/shape_from_shading/src/main.cpp:27-38; BASELINE config 3 is 1024^2).  Same protocol as iw_onchip.h, re-cut for a 5 x 5 coupling:
@@ -21,7 +21,7 @@
 // Every wait is bounded by the device's wall clock; a time-out raises `bad`, every workgroup leaves the loop at its next sum, nothing is written to delta and the
 // host redoes the linear solve with the marching kernels.  The grid must be co-resident (one workgroup per CU): the launcher checks workgroups <= CUs.
 #pragma once
-#include "onchip_sync.h"
+#include "onchip_launch.h"
 
 namespace optamd {
 namespace {
@@ -44,7 +44,7 @@ struct SfsOcArgs {
     int* bad; long long timeoutTicks; int failAt;
     long long firstTicks;      // bound of the FIRST iteration's wait: the co-residency check (every workgroup has posted its words once it passes), before anything is written
     T qTolerance;
-    int* hostErr;                       // LM (the solver applies the update itself): pinned host word a workgroup that gave up raises on its way out; GN: nullptr (sfs_applyDelta tells the host)
+    int* hostErr;                       // LM (the solver applies the update itself): pinned host word a workgroup that gave up raises on its way out; GN: nullptr (ocApplyDelta tells the host)
     long long* prof;                    // SO_PROFILE builds: [G][8] ticks per phase (wave 0 of every workgroup), else nullptr
     double* lmBreak;                    // pinned {iteration + 1, zeta} of the q early-out (OnChipLm::breakInfo), or nullptr
 };
@@ -440,16 +440,6 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
             if (y < A.H) K.delta[y * A.W + x] = DL_LDS ? dlL[(DL_LDS ? i : 0) * kSoBlock + tid] : dl[DL_LDS ? 0 : i];
         }
     }
-}
-
-// PCGLinearUpdate X += delta (solver.t:552-557) behind the on-chip Gauss-Newton solve -- unless a wait timed out: then the unknowns stay untouched and the host is told
-template <class T>
-__global__ __launch_bounds__(kBlock) void sfs_applyDelta(T* __restrict__ X, const T* __restrict__ delta, long N, const int* __restrict__ bad, int* hostErr) {
-    if (__hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(hostErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < N; i += (long)gridDim.x * blockDim.x) X[i] = X[i] + delta[i];
 }
 
 }  // namespace

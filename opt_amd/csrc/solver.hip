@@ -360,8 +360,7 @@ struct PcgSolver : SolverBase {
         n = E->nScalars; nPad = (n + 3) / 4 * 4; nPacks = nPad / PackN<T>::N;
         int dev = 0, cus = 256; HIP_CHECK(hipGetDevice(&dev));
         HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        long want = (nPacks + kBlock - 1) / kBlock;
-        streamGrid = (int)std::max<long>(1, std::min<long>(want, std::min<long>(kMaxPartials, (long)cus * 8)));
+        streamGrid = flatGrid(nPacks, cus, kMaxPartials);
         delta = allocVec(); r = allocVec(); z = allocVec(); p = allocVec(); Ap_X = allocVec(); CtC = allocVec(); preconditioner = allocVec();
         if (lm) { b = allocVec(); Adelta = allocVec(); SSq = allocVec(); prevX = allocVec(); }
         p2 = allocVec();
@@ -721,13 +720,13 @@ struct PcgSolver : SolverBase {
         usedOnChip = true; unknownsUpdated = true; return true;
     }
     // One GPU: the whole linear solve as one persistent launch with the loop state on chip, if the kernel set has one and the problem fits (iw_onchip.h, sfs_onchip.h,
-    // stencil_onchip.h).  Gauss-Newton (lmc == nullptr): it may end with PCGLinearUpdate (EnergyOps::onChipAppliedUpdate); a traced solve gets its per-iteration
+    // stencil_onchip.h).  Gauss-Newton (lmc == nullptr): it ends with PCGLinearUpdate, guarded by the launch's failure word; a traced solve gets its per-iteration
     // scalars from the kernel.  Levenberg-Marquardt: CtC, the q early-out and the split residual reset happen on chip, the host sees only delta -- and, for a
     // listening caller (verbosity > 0), the iteration and zeta of the early-out in a pinned word, from which the reference's "breaking at iteration" message is
     // printed once the step has drained (afterLinearSolve; verbose and silent runs take the SAME path).  Not reproduced there: the message of an early-out decided
     // after the LAST iteration (its test is dead -- the loop has ended -- and the on-chip kernels do not form it).
     bool tryOnChip(const T* preArg, const OnChipLm<T>* lmc) {
-        if (!((preArg || E->onChipWithoutPreconditioner()) && onChipAllowed() && sp.lIterations > 0 && takeLease())) return false;
+        if (!((preArg || chip) && onChipAllowed() && sp.lIterations > 0 && takeLease())) return false;
         double* tr = nullptr;
         if (traceEnabled) {
             if (onChipTraceCap < sp.lIterations) { if (onChipTrace) HIP_CHECK(hipFree(onChipTrace)); onChipTraceCap = sp.lIterations; HIP_CHECK(hipMalloc((void**)&onChipTrace, sizeof(double) * 4 * onChipTraceCap)); }
@@ -737,7 +736,7 @@ struct PcgSolver : SolverBase {
         if (lmc) { if (!lmBreak) lmBreak = (double*)allocPinned(64); lmBreak[0] = 0.0; lmBreak[1] = 0.0; la.breakInfo = verbosity > 0 ? lmBreak : nullptr; }
         if (!E->pcgSolveOnChip(r, p, delta, sp.lIterations, tr, lmc ? &la : nullptr, ctx)) { dropLease(); return false; }
         usedOnChip = true;
-        if (!lmc) unknownsUpdated = E->onChipAppliedUpdate();
+        if (!lmc) unknownsUpdated = true;
         if (traceEnabled) {
             std::vector<double> h(4 * (size_t)sp.lIterations);
             HIP_CHECK(hipMemcpyAsync(h.data(), onChipTrace, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
@@ -1151,9 +1150,7 @@ struct PcgSolver : SolverBase {
             exchangeVector(delta);
             E->evalModelCost(delta, distributed ? redA : redMH, ctx);   // (its own partials buffer: the value is read together with the new cost below)
             imageOp(3);   // savePreviousUnknowns + PCGLinearUpdate
-        } else if (!unknownsUpdated) {   // PCGLinearUpdate (behind an on-chip solve that left the update to the solver: guarded by the launch's failure word where the kernel set can)
-            if (!(usedOnChip && E->onChipGuardedUpdate(delta, ctx))) imageOp(0);
-        }
+        } else if (!unknownsUpdated) imageOp(0);   // PCGLinearUpdate
         exchangeUnknowns();
         E->precompute(ctx);
         if (lm && !distributed) {

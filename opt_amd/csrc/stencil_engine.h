@@ -242,7 +242,7 @@ struct StencilOps : EnergyOps<T> {
     void precompute(LaunchCtx& ctx) override {
         if constexpr (E::NAUX > 0) { ScopedKernel k(ctx, "precompute"); se_precompute<T, E><<<grid(), kBlock, 0, ctx.stream>>>(e); }
     }
-    int grid() const { const long n = (long)e.W * e.H * e.D; return (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, std::min<long>(kMaxPartials, (long)cus * 8))); }
+    int grid() const { return flatGrid((long)e.W * e.H * e.D, cus, kMaxPartials); }
     void bind(void** p, LaunchCtx&) override { e.bindParams(p); }
     T* unknownPtr(int img) const override { return const_cast<T*>(e.X[img]); }
     void evalCost(Reduction& out, LaunchCtx& ctx) override { ScopedKernel k(ctx, "computeCost"); se_cost<T, E><<<grid(), kBlock, 0, ctx.stream>>>(e, out.partials); out.n = grid(); }

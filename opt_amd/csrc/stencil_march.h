@@ -287,7 +287,7 @@ struct MarchLoop {
     }
     // After the last launch L-1 of a linear solve: the deferred term alpha_{L-2} p_{L-2} of an odd last launch; returns where p_{L-1} lives (the solver adds alpha_{L-1} p_{L-1})
     const T* finish(T* delta, long n, int cus, LaunchCtx& ctx) {
-        return ring.finish(delta, n, (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, (long)cus * 8)), ctx);
+        return ring.finish(delta, n, flatGrid(n, cus, cus * 8L), ctx);
     }
 };
 

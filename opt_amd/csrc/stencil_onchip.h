@@ -11,7 +11,7 @@
 //           picked up by the ring holders inside the ONE wait per iteration that also carries the four sums (alphaNum, alphaDen, s2, s3; beta by expansion as in
 //           march_pcgIter, including the reference's start: p_0 = r_0 / 4, alphaNumerator_0 = r_0 . p_0, so sum r_0^2 = 4 alphaNumerator_0 exactly);
 //   sums    every workgroup posts its partial sums as tagged words and adds ALL workgroups' words in the same order: the same bits everywhere.
-// Every wait is bounded by the device's wall clock; a time-out raises `bad`, nothing is written to delta, the unknowns stay untouched (march_applyDelta checks the flag) and
+// Every wait is bounded by the device's wall clock; a time-out raises `bad`, nothing is written to delta, the unknowns stay untouched (ocApplyDelta checks the flag) and
 // the host redoes the linear solve with the marching kernels.  The grid must be co-resident (one workgroup per CU): the launcher checks workgroups <= CUs.
 // Levenberg-Marquardt (LM = true): + CtC p (o.t:2076-2082; CtC as PCGFinalizeDiagonal left it, the start p_0 = M_LM r_0 comes from the solver, later z = r), a fifth sum --
 // sum r_0^2 in iteration 0, then Q_k = 1/2 sum delta . (r + b) (solver.t:483-485) formed where iteration k is applied and carried by the sums of iteration k + 1 -- and the
@@ -19,7 +19,7 @@
 // on the generic kernels.  Op::kSplit31 (intrinsic_image_decomposition: two unknown images) only changes where a pixel's scalars sit in the solver's vectors.
 #pragma once
 #include "stencil_march.h"
-#include "onchip_sync.h"
+#include "onchip_launch.h"
 
 namespace optamd {
 namespace {
@@ -324,111 +324,86 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
     }
 }
 
-// PCGLinearUpdate X += delta (solver.t:552-557) behind the on-chip solve -- unless a wait timed out: then the unknowns stay untouched and the host is told
-template <class T>
-__global__ __launch_bounds__(kBlock) void march_applyDelta(T* __restrict__ X, const T* __restrict__ delta, long n, const int* __restrict__ bad, int* hostErr) {
-    if (__hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(hostErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
+// ---- host side: the family's data for onchip_launch.h ----------------------------------------------------------------------------------------------------------
+constexpr OcFamily kMoFamily{kMoSpan, 2, kMoMaxG, kMoNWMax, "march_onchipPcg", "march_pcgIter", "generic kernels", nullptr};
+
+template <class T, class Op, int R, int WV, bool LM> constexpr size_t moLdsBytes() {      // A p and delta (where they wait in LDS) + b (LM) + the sums' staging
+    const size_t plane = (size_t)R * Op::C * sizeof(T) * WV * kWave;
+    const bool apLds = Op::C * sizeof(T) * R >= 128, dlLds = apLds && Op::kCoef >= 4 && (Op::C + Op::kCoef) * sizeof(T) * R >= 256;
+    return (apLds ? plane : 0) + (dlLds ? plane : 0) + (LM ? plane : 0) + 12 * 1024;
+}
+// a variant whose registers do not hold its loop state is not instantiated (Op::spills, from the compiler's resource remarks); should a compiler upgrade make another one
+// spill it is still not offered (hipFuncGetAttributes): no scratch in a kernel that is all latency
+template <class T, class Op, int R, int WV, bool LM> const void* moKernel() {
+    if constexpr (moLdsBytes<T, Op, R, WV, LM>() <= 150 * 1024 && !Op::template spills<R, WV, LM>()) {
+        const void* fn = (const void*)march_onchipPcg<T, Op, R, WV, LM>;
+        hipFuncAttributes fa{};
+        if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.localSizeBytes == 0) return fn;
+        (void)hipGetLastError();
     }
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) X[i] = X[i] + delta[i];
+    return nullptr;
+}
+template <class T, class Op> const std::vector<OcVariant>& moVariants() {
+    static const std::vector<OcVariant> v = [] {
+        std::vector<OcVariant> o;
+#define MO_VARIANT(R, WV) o.push_back({R, WV, moKernel<T, Op, R, WV, false>(), moKernel<T, Op, R, WV, true>()})
+        MO_VARIANT(2, 4); MO_VARIANT(4, 4); MO_VARIANT(8, 4); MO_VARIANT(2, 8); MO_VARIANT(4, 8); MO_VARIANT(8, 8);
+        if constexpr (Op::C * sizeof(T) <= 8) { MO_VARIANT(16, 4); MO_VARIANT(16, 8); }
+#undef MO_VARIANT
+        return o;
+    }();
+    return v;
 }
 
-// Host side: buffers, variant choice, launch.  The switches (OPT_AMD_ONCHIP*) and the time-out verdict: `guard` (onchip_sync.h OnchipGuard).
-template <class T>
-struct OnchipMarch {
-    OnchipGuard guard;
-    oc_u64 *slots = nullptr, *box = nullptr;      // the tagged buffers
-    // The buffers of the path, sized for the plan's image (the dimensions of a plan are fixed).  Called when the plan is made (the kernel set's constructor), so that the
-    // first linear solve of a plan does not pay for four allocations; solve() calls it itself if nobody has.
-    // ... only for plans that can take the path at all: some variant of THIS operator fits THIS device's CUs for the image (a 4-channel double image of
-    // 1-2 M pixels used to allocate ~256 MB of tagged box it could never use)
-    template <class Op> void reserveFor(int W, int H, int cus) {
-        int sx, ty, G;
-        if (select<Op, false>(W, H, cus, sx, ty, G) || select<Op, true>(W, H, cus, sx, ty, G)) reserve(W, H, Op::C);
+// ---- a kernel set whose Gauss-Newton PCG loop runs on the marching template (stencil_march.h MarchLoop) and whose whole linear solve goes on chip where it fits:
+// the EnergyOps side of both, once.  The kernel set supplies the operator object, the image, its flag image (or none), its enable switch and -- Op::kCoef > 0 --
+// the pass that produces the operator's per-pixel coefficients (run on the first launch of a loop and in front of an on-chip solve).
+template <class T, class Op, class Base>
+struct MarchOps : Base {
+    using Base::Base;
+    MarchLoop<T> march; OnchipLauncher<T> oc;
+    int mW = 0, mH = 0, mCus = 0;
+    bool useMarch = true, movableWhenOff = false;      // the enable switch; deltaMovable() with the switch off
+    const uint8_t* marchFlags = nullptr;               // Op::kMasked: bit 0 = the pixel is an unknown
+    T* coef = nullptr;
+    virtual Op marchOp() const = 0;
+    virtual void marchCoefficients(T* /*coef*/, LaunchCtx&) {}
+    // enableSwitch: the environment variable that switches both paths off (nullptr: none); updateCap: workgroups of the guarded update per unknown image
+    void marchInit(int W, int H, int cus, const char* enableSwitch, bool movableOff, long updateCap) {
+        mW = W; mH = H; mCus = cus; movableWhenOff = movableOff;
+        if (const char* e = enableSwitch ? getenv(enableSwitch) : nullptr) useMarch = atoi(e) != 0;
+        oc.init(kMoFamily, moVariants<T, Op>, W, H, Op::C, cus, updateCap);
+        if (useMarch) oc.reserve();
     }
-    void reserve(int W, int H, int C) {
-        if (slots || !guard.enabled || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return;
-        if ((long)W * H > (long)kMoMaxG * 8 * kMoSpan * 16 || divUp(W, kMoSpan) > kMoMaxG * 8) return;      // (more pixels than the largest variant holds on the largest grid: the path will never be taken)
-        slots = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)kMoMaxG * kMoNWMax);
-        box = guard.allocTagged<oc_u64>(sizeof(oc_u64) * 2 * (size_t)W * H * C * (sizeof(T) / 4));
-        guard.allocWords(nullptr); guard.clearTagged(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr));      // (done before the plan's own stream sees the buffers)
-    }
-    struct Variant { int rows, waves; const void* fn; };
-    template <class Op, int R, int WV, bool LM> static constexpr size_t ldsBytes() {      // A p and delta (where they wait in LDS) + b (LM) + the sums' staging
-        const size_t plane = (size_t)R * Op::C * sizeof(T) * WV * kWave;
-        const bool apLds = Op::C * sizeof(T) * R >= 128, dlLds = apLds && Op::kCoef >= 4 && (Op::C + Op::kCoef) * sizeof(T) * R >= 256;
-        return (apLds ? plane : 0) + (dlLds ? plane : 0) + (LM ? plane : 0) + 12 * 1024;
-    }
-    template <class Op, bool LM> static const std::vector<Variant>& variants() {
-        static const std::vector<Variant> v = [] {
-            std::vector<Variant> o;
-#define MO_VARIANT(R, WV) if constexpr (ldsBytes<Op, R, WV, LM>() <= 150 * 1024 && !Op::template spills<R, WV, LM>()) o.push_back({R, WV, (const void*)march_onchipPcg<T, Op, R, WV, LM>})
-            MO_VARIANT(2, 4); MO_VARIANT(4, 4); MO_VARIANT(8, 4); MO_VARIANT(2, 8); MO_VARIANT(4, 8); MO_VARIANT(8, 8);
-            if constexpr (Op::C * sizeof(T) <= 8) { MO_VARIANT(16, 4); MO_VARIANT(16, 8); }
-#undef MO_VARIANT
-            // a variant whose registers do not hold its loop state is not instantiated (Op::spills, from the compiler's resource remarks); should a compiler upgrade make another one
-            // spill it is still not offered: no scratch in a kernel that is all latency
-            std::vector<Variant> ok;
-            for (const auto& v : o) { hipFuncAttributes fa{}; if (hipFuncGetAttributes(&fa, v.fn) == hipSuccess && fa.localSizeBytes == 0) ok.push_back(v); else (void)hipGetLastError(); }
-            return ok;
-        }();
-        return v;
-    }
-    // among the variants whose workgroups fit one per CU: the least marching time per SIMD and iteration
-    template <class Op, bool LM = false> const Variant* select(int W, int H, int cus, int& stripsX, int& tilesY, int& G) const {
-        stripsX = divUp(W, kMoSpan);
-        const Variant* best = nullptr; int bestCost = 1 << 30;
-        for (const auto& v : variants<Op, LM>()) {
-            if (guard.forceRows && v.rows != guard.forceRows) continue;
-            if (guard.forceWaves && v.waves != guard.forceWaves) continue;
-            const int ty = divUp(H, v.rows), g = divUp(stripsX * ty, v.waves);
-            if (g > std::min(cus, kMoMaxG)) continue;
-            const int cost = (v.waves == 4 ? 100 : 136) * (v.rows + 2);      // (measured: two waves per SIMD march a row pair in 1.36 of the time one wave marches a row)
-            if (cost < bestCost) { best = &v; bestCost = cost; tilesY = ty; G = g; }
+    ~MarchOps() override { if (coef) (void)hipFree(coef); }
+    void produceCoefficients(LaunchCtx& ctx) {
+        if constexpr (Op::kCoef > 0) {
+            if (!coef) HIP_CHECK(hipMalloc((void**)&coef, (size_t)Op::kCoef * mW * mH * sizeof(T)));
+            ScopedKernel k(ctx, "operatorCoefficients");
+            marchCoefficients(coef, ctx);
         }
-        return best;
     }
-    // the whole linear solve + X += delta; false (nothing touched): not offered for this plan
-    // lm: Levenberg-Marquardt (the solver applies the update itself and hears of a time-out through the guard's hostErr)
-    template <class Op> bool solve(const Op& op, int W, int H, const uint8_t* flags, const T* coef, const T* r0, const T* p0, T* delta, T* X, int L, int cus, LaunchCtx& ctx,
-                                   const OnChipLm<T>* lm = nullptr) {
-        constexpr int C = Op::C;
-        if (!guard.usable() || L <= 0 || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return false;
-        if (lm && (!lm->CtC || lm->resetPeriod < L)) return false;      // a split residual reset before the last iteration: the generic kernels' business
-        int stripsX = 0, tilesY = 0, G = 0;
-        const Variant* V = lm ? select<Op, true>(W, H, cus, stripsX, tilesY, G) : select<Op, false>(W, H, cus, stripsX, tilesY, G);
-        if (!V) return false;
-        if (!slots) { reserve(W, H, C); if (!slots) return false; }
-        const unsigned tag0 = guard.tags((unsigned)L, ctx.stream);
-        const OcTimeouts tmo = guard.timeouts(L, false);
-        MoArgs<T> K{W, H, r0, p0, delta, flags, coef, stripsX, tilesY, G, L, tag0, slots, box, guard.bad, tmo.later, guard.failAtThisLaunch(), tmo.first, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0),
-                    (lm || !X) ? guard.hostErr : nullptr, lm ? lm->breakInfo : nullptr};      // (no X: the solver applies the update itself, as for LM)
-        {
-            ScopedKernel k(ctx, "PCGSolveOnChip");
-            Op opc = op;
-            void* kargs[] = {(void*)&opc, (void*)&K};
-            if (hipLaunchKernel(V->fn, dim3(G), dim3(V->waves * kWave), kargs, 0, ctx.stream) != hipSuccess) { (void)hipGetLastError(); guard.enabled = false; return false; }
-        }
-        if (!lm && X) {
-            ScopedKernel k(ctx, "PCGLinearUpdate");
-            const long n = (long)W * H * C;
-            const int grid = (int)std::max<long>(1, std::min<long>((n + kBlock - 1) / kBlock, (long)cus * 8));
-            march_applyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(X, delta, n, guard.bad, guard.hostErr);
-        }
-        guard.launched = true;
-        return true;
+    bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
+        if (!useMarch || a.pre || a.CtC) return false;      // Gauss-Newton only: the Levenberg-Marquardt loop keeps the generic kernels
+        if (a.first) produceCoefficients(ctx);
+        return march.launch(marchOp(), mW, mH, marchFlags, mCus, a, ctx, coef);
     }
-    template <class Op> std::string describe(int W, int H, int cus, int L, bool lmv, const char* marchName) const {
-        int stripsX = 0, tilesY = 0, G = 0;
-        const Variant* V = (guard.usable() && L > 0) ? (lmv ? select<Op, true>(W, H, cus, stripsX, tilesY, G) : select<Op, false>(W, H, cus, stripsX, tilesY, G)) : nullptr;
-        char buf[500];
-        if (V) snprintf(buf, sizeof buf, "path=on-chip (march_onchipPcg%s); onchip_rows_per_wave=%d; waves_per_workgroup=%d; wave_tiles=%dx%d of 62 x %d pixels; workgroups=%d of %d CUs; fallback=one launch per PCG iteration (%s)",
-                        lmv ? ", LM while lIterations <= residual_reset_period" : "", V->rows, V->waves, stripsX, tilesY, V->rows, G, cus, lmv ? "generic kernels" : marchName);
-        else snprintf(buf, sizeof buf, "path=one launch per PCG iteration (%s); why_not_on_chip=%s", lmv ? "generic kernels, LM" : marchName,
-                      guard.whyOff() ? guard.whyOff() : "the wave tiles do not fit the CUs");
-        return buf;
+    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, (long)Op::C * mW * mH, mCus, ctx); }
+    bool deltaMovable() const override { return (useMarch || movableWhenOff) && !this->slab.active; }      // (the march takes delta from its arguments at every launch: PcgSolver::deltaTrial)
+    // the whole linear solve on chip, X += delta behind a Gauss-Newton one included (onchip_launch.h)
+    bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
+        if (!useMarch || traceDev || this->slab.active || !oc.plan(L, lm != nullptr, lm)) return false;      // (asked before the coefficient pass is spent)
+        produceCoefficients(ctx);
+        return oc.solve(L, lm, delta, *this, ctx, [&](const OcGrant& g) {
+            MoArgs<T> K{mW, mH, r0, p0, delta, marchFlags, coef, g.stripsX, g.tilesY, g.G, L, g.tag0, g.slots, g.box, g.bad, g.tmo.later, g.failAt, g.tmo.first, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0),
+                        g.hostErr, lm ? lm->breakInfo : nullptr};
+            Op op = marchOp();
+            void* kargs[] = {(void*)&op, (void*)&K};
+            return g.launch(kargs, ctx.stream);
+        });
     }
+    OnchipGuard* onChipGuard() override { return &oc.guard; }
+    std::string describe(int L, bool lmv) override { return oc.describe(useMarch ? L : 0, lmv); }
 };
 
 }  // namespace

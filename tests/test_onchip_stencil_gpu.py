@@ -207,8 +207,8 @@ def test_lm_timeout_path(oracle_lib, monkeypatch, fail_at):
     _lm_side_by_side(oracle_lib, _poisson(130, 70, True, 3, "random"), 3, 10, 1e-10, 1e-9, 1e-8, expect_onchip=True, status=2, q_tolerance=-1e9)
 
 
-# ---- intrinsic_image_decomposition: two unknown images (3 + 1 channels per pixel: the solver's split layout), four operator coefficients per pixel; the update is
-# applied by the solver (the caller's two arrays need not be consecutive) ---------------------------------------------------------------------------------------------
+# ---- intrinsic_image_decomposition: two unknown images (3 + 1 channels per pixel: the solver's split layout), four operator coefficients per pixel; the guarded
+# update runs per unknown image (the caller's two arrays need not be consecutive) ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("liters", [1, 3, 12])
 @pytest.mark.parametrize("rows,waves", [(2, 4), (4, 4), (2, 8)])
 @pytest.mark.parametrize("W,H", [(7, 9), (61, 5), (62, 3), (63, 9), (300, 40), (64, 300)])

@@ -73,7 +73,9 @@ void OptAmd_PlanGetTrace(Opt_Plan* plan, double* rows6);
 double OptAmd_PlanTrustRegionRadius(Opt_Plan* plan);
 
 /* Which linear-solve path the plan's last step took:
- *   0  launch-per-iteration kernels (the problem does not fit the chip, the kernel set has no on-chip solve, or it is switched off: "amd_onchip" / "amd_reference_order");
+ *   0  launch-per-iteration kernels (the problem does not fit the chip, the kernel set has no on-chip solve, it is switched off: "amd_onchip" = 0 / "amd_reference_order",
+ *      or a Levenberg-Marquardt solve passes a residual reset -- lIterations > residual_reset_period -- on a kernel set that keeps such a solve on chip only with
+ *      "amd_onchip" = 2);
  *   1  the whole linear solve of the last step ran as one persistent on-chip launch;
  *   2  the plan is in its back-off after a failed on-chip launch: the waits of a launch's first phase are bounded by 10 ms (passing them proves the whole grid resident;
  *      a foreign tenant holding CUs makes the launch give up there, before anything has been written), the step was redone by the streaming kernels (reported on stderr the
@@ -92,7 +94,12 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          r, z and A p in memory and form the three sums as the reference does (beta numerator = r.z directly).  This is the loop that meets the 1e-5
  *                          (float) contract against the oracle at every horizon tested (400 PCG iterations included); it moves the reference formulation's 180 B/pixel
  *                          per iteration where the default single-kernel iteration moves 53 and it never runs on chip.  0 (default): the fused loops.
- *   "amd_onchip"           0: never take the on-chip (persistent) linear solve; 1 (default): take it where the problem fits the chip.
+ *   "amd_onchip"           0: never take the on-chip (persistent) linear solve; 1 (default): take it where the problem fits the chip.  2: as 1, and the 5-point-stencil
+ *                          energies (poisson_image_editing, optical_flow, intrinsic_image_decomposition, the minimal laplacian) also keep a Levenberg-Marquardt solve
+ *                          on chip when a residual reset falls inside it (lIterations > residual_reset_period > 0): the reference's split PCGStep2
+ *                          (solverGPUGaussNewton.t:1077-1086) runs inside the launch.  The reference's own callers sit there (poisson_image_editing: 100 linear iterations,
+ *                          optical_flow: 50, period 10).  It is opt-in because the two paths round differently (see OptAmd_PlanOnChipStatus).  image_warping resets on chip
+ *                          under 1 and 2 alike; shape_from_shading keeps such a solve on the launch-per-iteration loop under both.
  * OptAmd_PlanDescribe reports the choice.  (The environment switches OPT_AMD_ONEKERNEL / OPT_AMD_ONCHIP remain as process-wide development overrides.) */
 
 /* The float4 copy rate of this box in GB/s: `bytes` moved in total per repetition (half read, half written; device memory allocated and freed inside the call),

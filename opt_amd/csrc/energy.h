@@ -103,6 +103,7 @@ struct LmInitArgs {
 // Levenberg-Marquardt controls of EnergyOps::pcgSolveOnChip: the scalars of PCGFinalizeDiagonal (solver.t:631-664), q_tolerance and residual_reset_period (:1077-1102).
 template <class T>
 struct OnChipLm { T radius, minLm, maxLm, qTolerance; int resetPeriod; const T* CtC = nullptr;
+                  int onchip = 1;                  // the plan's amd_onchip: 2 = a residual reset inside the solve (resetPeriod < lIterations) may stay on chip where the kernel family has that mode
                   double* breakInfo = nullptr; };      // pinned, 2 doubles: workgroup 0 leaves {iteration of the q early-out + 1, zeta} there (0: the loop ran to its end) -- the solver prints the
                                                        // reference's "breaking at iteration" message from it when someone listens (verbosity > 0)      // CtC: the clamped diagonal PCGFinalizeDiagonal has just written (energies whose kernel does not rebuild it from a table)
 
@@ -189,7 +190,7 @@ struct EnergyOps {
     virtual void onChipApply(const T* /*delta*/, const double* /*verdict*/, bool /*refused*/, LaunchCtx&) {}
     // OptAmd_PlanDescribe: which linear-solve path the kernel set would take for the plan as it stands (dims, slab), as "key=value; ..." -- bench.py --dry prints it per
     // rank so that a multi-GPU run can be read before it is started.
-    virtual std::string describe(int /*lIterations*/, bool /*lm*/) { return "path=launch-per-iteration"; }
+    virtual std::string describe(int /*lIterations*/, bool /*lm*/, const OnChipLm<T>* /*lmControls: what the next LM step would pass to pcgSolveOnChip, or nullptr*/) { return "path=launch-per-iteration"; }
     // The time-out protocol of pcgSolveOnChip (onchip_sync.h OnchipGuard): after the stream has drained the solver asks it whether a wait inside the last on-chip solve timed out
     // (another tenant on the GPU kept the workgroups from being co-resident) -- then the unknowns were left untouched, the path is off for this plan and the solver redoes
     // the linear solve -- and switches the path back on after its back-off.  nullptr: the kernel set has no on-chip solve.

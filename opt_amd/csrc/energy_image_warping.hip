@@ -542,7 +542,7 @@ struct ImageWarpingOps : EnergyOps<T> {
         iw_applyDelta<T><<<flatGrid(N), kBlock, 0, ctx.stream>>>(const_cast<T*>(A.Offset), const_cast<T*>(A.Angle), delta, N, guard.bad, verdict, guard.hostErr, guard.stepWord());
         guard.launched = true;
     }
-    std::string describe(int L, bool lmv) override {      // ("key=value; ..." -- no ';' inside a value)
+    std::string describe(int L, bool lmv, const OnChipLm<T>*) override {      // ("key=value; ..." -- no ';' inside a value; the LM variants do the residual reset on chip whatever the controls)
         const Slab& sl = this->slab;
         const int rowsOwned = (sl.active ? sl.yEnd - sl.yBegin : A.H);
         char buf[900];

@@ -797,7 +797,7 @@ struct SfsOps : EnergyOps<T> {
             return true;
         });
     }
-    std::string describe(int L, bool lmv) override { return oc.describe(L, lmv, this->slab.active ? "row slabs" : nullptr); }
+    std::string describe(int L, bool lmv, const OnChipLm<T>* lmc) override { return oc.describe(L, lmv, lmc, this->slab.active ? "row slabs" : nullptr); }
 };
 
 template <class T> EnergyOps<T>* makeSfs(const unsigned* dims) { return new SfsOps<T>(dims); }

@@ -9,7 +9,11 @@
 namespace optamd {
 namespace {
 
-struct OcVariant { int rows, waves; const void *gn, *lm; };      // rows a wave owns, waves per workgroup, the Gauss-Newton / Levenberg-Marquardt kernel (nullptr: not offered)
+// rows a wave owns, waves per workgroup, the kernel of each mode (nullptr: not offered): Gauss-Newton, Levenberg-Marquardt, Levenberg-Marquardt with the split residual reset inside the solve
+struct OcVariant {
+    int rows, waves; const void *gn, *lm, *lmReset = nullptr;
+    const void* kernel(int mode) const { return mode == 0 ? gn : mode == 1 ? lm : lmReset; }
+};
 struct OcFamily {
     int span, halo, maxG, words;             // pixels a wave owns per row; rows it holds around its own (the cost model); workgroup cap; tagged words per workgroup
     const char *kernel, *loopGN, *loopLM;    // describe(): the kernel, the launch-per-iteration loops it stands in for
@@ -17,6 +21,7 @@ struct OcFamily {
 };
 struct OcPlan {
     const OcVariant* V = nullptr; int stripsX = 0, tilesY = 0, G = 0;
+    int mode = 0, phases = 0;      // the variant's kernel (OcVariant::kernel); grid-wide waits of the solve: one per iteration and one more per in-solve residual reset (mode 2)
     explicit operator bool() const { return V != nullptr; }
 };
 // What a family fills its kernel's argument struct from; launch() is the launch of the chosen variant.
@@ -36,27 +41,34 @@ struct OnchipLauncher {
     long updateCap = 0;                    // workgroups of the guarded update, per unknown image
     void init(const OcFamily& f, const std::vector<OcVariant>& (*v)(), int W_, int H_, int C_, int cus_, long updateCap_) { fam = f; variants = v; W = W_; H = H_; C = C_; cus = cus_; updateCap = updateCap_; }
     // among the variants whose workgroups fit one per CU: the least marching time per SIMD and iteration
-    OcPlan select(bool lm) const {
+    OcPlan select(int mode) const {
         OcPlan best; int bestCost = 1 << 30;
         const int stripsX = divUp(W, fam.span);
         for (const auto& v : variants()) {
-            if (!(lm ? v.lm : v.gn)) continue;
+            if (!v.kernel(mode)) continue;
             if (guard.forceRows && v.rows != guard.forceRows) continue;
             if (guard.forceWaves && v.waves != guard.forceWaves) continue;
             const int ty = divUp(H, v.rows), g = divUp(stripsX * ty, v.waves);
             if (g > std::min(cus, fam.maxG)) continue;
             const int cost = (v.waves == 4 ? 100 : 136) * (v.rows + fam.halo);      // (measured: two waves per SIMD march a pair of trips in 1.36 of the time one wave marches one)
-            if (cost < bestCost) { best = OcPlan{&v, stripsX, ty, g}; bestCost = cost; }
+            if (cost < bestCost) { best = OcPlan{&v, stripsX, ty, g, mode, 0}; bestCost = cost; }
         }
         return best;
     }
     // THE predicate: would a linear solve of L iterations run on chip, and with which variant?  lmv: the Levenberg-Marquardt loop (lm: its controls, where the caller has
-    // them -- a split residual reset before the last iteration is the launch-per-iteration loop's business).  solve(), describe(), reserve() and a kernel set that wants
-    // to know before it spends a coefficient pass all ask here.
+    // them).  A split residual reset before the last iteration (residual_reset_period < L) takes the family's mode-2 kernel, for a caller who opted in (amd_onchip = 2)
+    // and where such a variant fits; otherwise it is the launch-per-iteration loop's business.  solve(), describe(), reserve() and a kernel set that wants to know before
+    // it spends a coefficient pass all ask here.
+    bool resetInside(int L, const OnChipLm<T>* lm) const { return lm && lm->resetPeriod < L; }
+    bool offersReset() const { for (const auto& v : variants()) if (v.lmReset) return true; return false; }
     OcPlan plan(int L, bool lmv, const OnChipLm<T>* lm = nullptr) const {
         if (!guard.usable() || L <= 0 || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return {};
-        if (lm && (!lm->CtC || lm->resetPeriod < L)) return {};
-        return select(lmv);
+        if (lm && !lm->CtC) return {};
+        if (!resetInside(L, lm)) { OcPlan P = select(lmv ? 1 : 0); P.phases = L; return P; }
+        if (lm->onchip < 2 || lm->resetPeriod <= 0) return {};
+        OcPlan P = select(2);
+        P.phases = L + (L - 1) / lm->resetPeriod;
+        return P;
     }
     // The buffers of the path, when the plan is made (so that its first linear solve does not pay for the allocations) -- only for plans that can take the path at all:
     // some variant fits this device's CUs for the image (a 4-channel double image of 1-2 M pixels would otherwise hold ~256 MB of tagged box it could never use)
@@ -73,7 +85,7 @@ struct OnchipLauncher {
         const OcPlan P = plan(L, lm != nullptr, lm);
         if (!P) return false;
         if (!slots) { reserve(); if (!slots) return false; }
-        OcGrant g{P, lm ? P.V->lm : P.V->gn, guard.tags((unsigned)L, ctx.stream), slots, box, guard.bad, guard.timeouts(L, false), guard.failAtThisLaunch(), lm ? guard.hostErr : nullptr};
+        OcGrant g{P, P.V->kernel(P.mode), guard.tags((unsigned)P.phases, ctx.stream), slots, box, guard.bad, guard.timeouts(P.phases, false), guard.failAtThisLaunch(), lm ? guard.hostErr : nullptr};
         {
             ScopedKernel k(ctx, "PCGSolveOnChip");
             if (!launchWith(g)) {      // (a device that cannot hold the variant's LDS: not offered again)
@@ -95,13 +107,21 @@ struct OnchipLauncher {
         return true;
     }
     // ("key=value; ..." -- no ';' inside a value)  blocked: the kernel set's own reason to keep the plan off the chip, or nullptr
-    std::string describe(int L, bool lmv, const char* blocked = nullptr) const {
-        const OcPlan P = blocked ? OcPlan{} : plan(L, lmv);
-        char buf[600];
+    // lm: the Levenberg-Marquardt controls the plan's next step would pass to solve() -- the answer is the step's
+    std::string describe(int L, bool lmv, const OnChipLm<T>* lm, const char* blocked = nullptr) const {
+        const OcPlan P = blocked ? OcPlan{} : plan(L, lmv, lm);
+        const bool reset = resetInside(L, lm);
+        char buf[700];
         if (P) snprintf(buf, sizeof buf, "path=on-chip (%s%s); onchip_rows_per_wave=%d; waves_per_workgroup=%d; wave_tiles=%dx%d of %d x %d pixels; workgroups=%d of %d CUs; fallback=one launch per PCG iteration (%s)",
-                        fam.kernel, lmv ? ", LM while lIterations <= residual_reset_period" : "", P.V->rows, P.V->waves, P.stripsX, P.tilesY, fam.span, P.V->rows, P.G, cus, lmv ? fam.loopLM : fam.loopGN);
+                        fam.kernel, !lmv ? "" : P.mode == 2 ? ", LM with the residual resets inside the solve" : ", LM, no residual reset inside the solve", P.V->rows, P.V->waves, P.stripsX, P.tilesY, fam.span,
+                        P.V->rows, P.G, cus, lmv ? fam.loopLM : fam.loopGN);
         else snprintf(buf, sizeof buf, "path=one launch per PCG iteration (%s%s); why_not_on_chip=%s", lmv ? fam.loopLM : fam.loopGN, lmv ? ", LM" : "",
-                      guard.whyOff() ? guard.whyOff() : blocked ? blocked : "the wave tiles do not fit the CUs");
+                      guard.whyOff() ? guard.whyOff() : blocked ? blocked : lm && !lm->CtC ? "no LM diagonal"
+                      : !reset || !select(1) ? "the wave tiles do not fit the CUs"
+                      : !offersReset() ? "a residual reset falls inside the solve (lIterations > residual_reset_period) and this kernel family has no on-chip reset"
+                      : lm->resetPeriod <= 0 ? "residual_reset_period <= 0"
+                      : lm->onchip < 2 ? "a residual reset falls inside the solve (lIterations > residual_reset_period) and amd_onchip=2 was not set"
+                      : "a residual reset falls inside the solve and no variant with the reset on chip fits the CUs");
         return buf;
     }
 };

@@ -1052,13 +1052,15 @@ struct PcgSolver : SolverBase {
         redC.n = streamGrid; redQ.n = streamGrid;
         return Init::generic;
     }
+    // The Levenberg-Marquardt controls an on-chip solve is asked with: solveLinear and describe pass the same, so that describe answers for the step
+    OnChipLm<T> lmControls() const { return OnChipLm<T>{trust_region_radius, min_lm_diagonal, max_lm_diagonal, (T)sp.q_tolerance, sp.residual_reset_period, CtC, sp.amd_onchip}; }
     // The one place that picks the linear solve's path, the first that takes it: (1) on chip -- in slab mode behind the vote every rank issues --, (2) the kernel set's
     // launch-per-iteration loop, (3) the reference-order loop.  (1) and (2) need singleKernelAllowed() (off with OPT_AMD_ONEKERNEL=0 or amd_reference_order=1), in LM
     // also OPT_AMD_ONEKERNEL_LM, one GPU and no trace.  A redo after an on-chip time-out stops short of (3): false, and the step runs again from its PCGInit1.
     bool solveLinear(const T* preArg, Init init, bool redo) {
         if (singleKernelAllowed()) {
             if (lm) {
-                const OnChipLm<T> la{trust_region_radius, min_lm_diagonal, max_lm_diagonal, (T)sp.q_tolerance, sp.residual_reset_period, CtC};
+                const OnChipLm<T> la = lmControls();
                 if (oneKernelLM && !distributed && !traceEnabled && (tryOnChip(preArg, &la) || runLaunchPerIterationLM(preArg))) return true;
             } else {
                 if (distributed ? trySlabOnChip(preArg) : tryOnChip(preArg, nullptr)) return true;
@@ -1258,8 +1260,8 @@ struct PcgSolver : SolverBase {
     int onChipStatus() const override { return onChipOff() ? 2 : lastStepOnChip ? 1 : 0; }
     std::string describe() override {
         std::string d = sp.amd_reference_order ? std::string("path=reference-order (PCGStep1 [+ the previous PCGStep3] and PCGStep2 per PCG iteration, r / z / A p in memory); amd_reference_order=1")
-                                               : E->describe(sp.lIterations, lm);
-        if (!sp.amd_reference_order && !sp.amd_onchip) d += "; amd_onchip=0";
+                                               : [&] { const OnChipLm<T> la = lmControls(); return E->describe(sp.lIterations, lm, lm ? &la : nullptr); }();
+        if (!sp.amd_reference_order && sp.amd_onchip != 1) d += "; amd_onchip=" + std::to_string(sp.amd_onchip);
         if (!sp.amd_reference_order && !oneKernel) d += "; OPT_AMD_ONEKERNEL=0 (reference-order loop by environment)";
         if (onChipFailures) d += "; onchip_fallbacks=" + std::to_string(onChipFailures) + "; onchip_backoff_steps_left=" + std::to_string(onChipOff() ? onChipBackoff - onChipCleanSteps : 0);
         // what Opt_ProblemSolve does beyond Init + Step by Step on this plan, and where the trial over delta's placement stands

@@ -15,8 +15,11 @@
 // the host redoes the linear solve with the marching kernels.  The grid must be co-resident (one workgroup per CU): the launcher checks workgroups <= CUs.
 // Levenberg-Marquardt (LM = true): + CtC p (o.t:2076-2082; CtC as PCGFinalizeDiagonal left it, the start p_0 = M_LM r_0 comes from the solver, later z = r), a fifth sum --
 // sum r_0^2 in iteration 0, then Q_k = 1/2 sum delta . (r + b) (solver.t:483-485) formed where iteration k is applied and carried by the sums of iteration k + 1 -- and the
-// q early-out (:1093-1102) decided by every workgroup from the same totals; a residual reset before the last iteration (lIterations > residual_reset_period) keeps the solve
-// on the generic kernels.  Op::kSplit31 (intrinsic_image_decomposition: two unknown images) only changes where a pixel's scalars sit in the solver's vectors.
+// q early-out (:1093-1102) decided by every workgroup from the same totals.  A residual reset before the last iteration (lIterations > residual_reset_period) keeps the
+// solve on the generic kernels by default; with the solver parameter amd_onchip = 2 it takes the kernel's third mode (MODE 2), which does the split reset (:1077-1086,
+// kernels :491-534) inside the launch: the wave also keeps delta of its ring pixels, and an iteration k with (k + 1) % residual_reset_period == 0, k + 1 < L ends with a
+// second stencil pass A delta, r = b - A delta, z = r and a second grid-wide wait (phase B) that carries sum r.r (beta's numerator) and Q and hands the ring holders the
+// new r itself; the zeta test of that iteration is taken right there.  Phases, not iterations, number the tags.  Op::kSplit31 (intrinsic_image_decomposition: two unknown images) only changes where a pixel's scalars sit in the solver's vectors.
 #pragma once
 #include "stencil_march.h"
 #include "onchip_launch.h"
@@ -41,13 +44,16 @@ struct MoArgs {
     long long firstTicks;      // bound of the FIRST iteration's wait: the co-residency check (every workgroup has posted its words once it passes), before anything is written
     const T* CtC; T qTolerance; int* hostErr;      // LM: the clamped diagonal, q_tolerance, the pinned word a workgroup that gave up raises (the solver applies the update itself)
     double* lmBreak;                               // pinned {iteration + 1, zeta} of the q early-out (OnChipLm::breakInfo), or nullptr
+    int resetPeriod;                               // MODE 2: every resetPeriod-th iteration (but the last) ends with the split residual reset
 };
 
 __device__ __forceinline__ float moFma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double moFma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
-template <class T, class Op, int R, int WAVES, bool LM>
+// MODE: 0 Gauss-Newton, 1 Levenberg-Marquardt, 2 Levenberg-Marquardt with the split residual reset inside the solve
+template <class T, class Op, int R, int WAVES, int MODE>
 __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T> K) {
+    constexpr bool LM = MODE != 0, RESET = MODE == 2;
     constexpr int kMoNS = LM ? 5 : 4, kMoNW = 2 * kMoNS;
     constexpr int C = Op::C, HR = R + 2, kBlk = WAVES * kWave, WPS = (int)sizeof(T) / 4;
     constexpr int kCoefN = Op::kCoef > 0 ? Op::kCoef : 1;
@@ -109,18 +115,75 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
     double accQ = 0;
     T Q0 = 0;      // fetchQ before the loop (solver.t:1050): delta = 0, so exactly 0
     const size_t boxStride = (size_t)N * C * WPS;
+    // RESET: an iteration that ends with the split residual reset (solverGPUGaussNewton.t:1077-1083) takes two trips through this loop, one per grid-wide wait: phase A as
+    // ever up to delta += alpha p, then phase B -- a second stencil pass, A delta, with r = b - A delta, z = r, sum r.r and Q, the new r of the tile's outermost rows /
+    // columns travelling in the words A p takes otherwise.  Phases, not iterations, number the tags and pick the parity.  State: delta of the ring rows above and below the
+    // tile (the side columns' delta is dl of lanes 0 and 63: every lane applies delta += alpha p to the R pixels of its column), the phases passed so far, whether this
+    // trip is a phase B, the alpha numerator of its phase A, and whether the Q of the iteration before travels with this trip's sums (after a reset it has been tested).
+    Vec dr[RESET ? 2 : 1];
+    if constexpr (RESET) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) { dr[0].v[c] = 0; dr[RESET ? 1 : 0].v[c] = 0; }
+    }
+    unsigned phase = 0;
+    bool phaseB = false, qPending = false;
+    T aNumA = 0;
 
-    for (int k = 0; k < K.L; ++k) {
-        const unsigned tag = K.tag0 + (unsigned)k;
+    for (int k = 0; k < K.L; k += phaseB ? 0 : 1) {
+        const unsigned tag = K.tag0 + (RESET ? phase : (unsigned)k);
         const int par = (int)(tag & 1u);
         oc_u64* const box = K.apBox + (size_t)par * boxStride;
         oc_u64* const slotPar = K.slots + (size_t)par * K.G * kMoNW;
         if (k == K.failAt && g == 0 && tid == 0) __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const bool first = k == 0;
+        const bool resetIt = RESET && k + 1 < K.L && (k + 1) % K.resetPeriod == 0;      // this iteration ends with the split residual reset: r is formed anew, nobody needs the ring's A p
 
         // ---- PCGStep1: A p_k on the owned pixels, with the four sums (march_pcgIter's expressions) --------------------------------------------------------------
         double accDen = 0, accNum = 0, acc2 = 0, acc3 = 0, accX = 0;      // accX (LM): sum r_0^2 in iteration 0, the Q of the iteration before in the others
-        if (!idle) {
+        if constexpr (RESET) {      // ---- phase B: computeAdelta + PCGStep2_2ndHalf (:566-571, 505-534): r = b - (J^T J + CtC) delta, with sum r.r (in accNum) and Q (in accX) ----
+            if (phaseB && !idle) {
+                auto deltaRow = [&](int h) -> Vec {
+                    if (h == 0) return dr[0];
+                    if (h == HR - 1) return dr[RESET ? 1 : 0];
+                    Vec d;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) d.v[c] = DL_LDS ? dlL[((DL_LDS ? h - 1 : 0) * C + c) * kBlk + tid] : dl[DL_LDS ? 0 : h - 1].v[c];
+                    return d;
+                };
+                Vec du = deltaRow(0), dc = deltaRow(1);
+#pragma unroll
+                for (int h = 1; h <= R; ++h) {
+                    const int y = yBase - 1 + h;
+                    const Vec dd = deltaRow(h + 1);
+                    const Vec dlft = marchShift<true>(dc), drgt = marchShift<false>(dc);
+                    Vec o = op.apply(dc, dlft, drgt, du, dd, hasL, hasR, y - 1 >= 0, y + 1 < K.H, cf[h]);
+                    const bool on = (onBits >> h) & 1u;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) { o.v[c] += ctc[h - 1].v[c] * dc.v[c]; o.v[c] = on ? o.v[c] : T(0); }
+                    if (writer && y < K.H) {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            const T bv = bL[((h - 1) * C + c) * kBlk + tid];
+                            const T rn = bv - o.v[c];
+                            r[h].v[c] = rn;
+                            accNum += (double)rn * (double)rn;
+                            accX += (double)(T(0.5) * (dc.v[c] * (rn + bv)));      // solver.t:483-485
+                        }
+                        if (h == 1 || h == R || lane == 1 || lane == kMoSpan) {
+                            const size_t i = (size_t)(pixBase + h * K.W) * C * WPS;
+#pragma unroll
+                            for (int c = 0; c < C; ++c) {
+                                if constexpr (WPS == 1) ocStore(box + i + c, tag, __float_as_uint((float)r[h].v[c]));
+                                else { const oc_u64 b = (oc_u64)__double_as_longlong((double)r[h].v[c]); ocStore(box + i + 2 * c, tag, (unsigned)b); ocStore(box + i + 2 * c + 1, tag, (unsigned)(b >> 32)); }
+                            }
+                        }
+                    }
+                    du = dc; dc = dd;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        if (!idle && !(RESET && phaseB)) {
 #pragma unroll
             for (int h = 1; h <= R; ++h) {
                 const int y = yBase - 1 + h;
@@ -138,7 +201,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
                         if (LM && first) accX += rr * rr;
                     }
                     // the tile's outermost rows / columns: to the tagged image, for whoever holds them as ring
-                    if (h == 1 || h == R || lane == 1 || lane == kMoSpan) {
+                    if (!resetIt && (h == 1 || h == R || lane == 1 || lane == kMoSpan)) {
                         const size_t i = (size_t)(pixBase + h * K.W) * C * WPS;
 #pragma unroll
                         for (int c = 0; c < C; ++c) {
@@ -151,9 +214,9 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
             }
         }
 
-        // ---- the grid-wide sums; the ring's A p is collected inside the wait ------------------------------------------------------------------------------------
+        // ---- the grid-wide sums; the ring's A p (phase B: the ring's new r) is collected inside the wait ----------------------------------------------------
         {
-            if (LM && !first) accX = accQ;
+            if (LM && !first && !(RESET && phaseB)) accX = accQ;
             double v4[kMoNS];
             v4[0] = accNum; v4[1] = accDen; v4[2] = acc2; v4[3] = acc3;
             if constexpr (LM) v4[4] = accX;
@@ -172,7 +235,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
             constexpr int kPer = (kMoMaxG * kMoNW + kBlk - 1) / kBlk;
             oc_u64 w[kPer];
             const int nW = K.G * kMoNW;
-            const bool lastIt = k + 1 == K.L;      // (after the last iteration only delta survives: nobody needs the ring)
+            const bool lastIt = k + 1 == K.L || (RESET && resetIt && !phaseB);      // (after the last iteration only delta survives: nobody needs the ring; nor in front of a reset)
             // Ring requests: every lane asks for its column's pixel of the rows above and below the tile; the two side columns are asked for by ONE lane per pixel
             // (lane h: the left neighbour of row h, lane 32 + h: the right one) and handed to lanes 0 / 63 through scalar registers afterwards -- a lane holds three
             // pixels' words during the wait instead of R + 2 (the difference is what lets 16 rows per wave fit).
@@ -228,7 +291,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
                     if (check()) break;
                     if ((++spins & 31u) == 0) {
                         if (__hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-                        if (wall_clock64() - t0 > (k == 0 ? K.firstTicks : to)) { __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                        if (wall_clock64() - t0 > (k == 0 && !(RESET && phaseB) ? K.firstTicks : to)) { __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                     }
                 }
             }
@@ -272,8 +335,32 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
         }
         const double aNumD = TOT[0], aDenD = TOT[1], s2 = TOT[2], s3 = TOT[3];
         if (reinterpret_cast<const int*>(TOT + kMoNS)[0]) { failed = true; break; }      // uniform over the workgroup: a wait timed out somewhere
+        if constexpr (RESET) {
+            ++phase;
+            if (phaseB) {
+                {      // the q test of THIS iteration: the split step delivers Q directly
+                    const T Q1 = (T)TOT[kMoNS - 1];
+                    const T zeta = T(k + 1) * (Q1 - Q0) / Q1;
+                    if (zeta < K.qTolerance) { if (K.lmBreak && blockIdx.x == 0 && tid == 0) { K.lmBreak[1] = (double)zeta; K.lmBreak[0] = (double)(k + 2); } break; }
+                    Q0 = Q1;
+                }
+                const T betaB = (aNumA > T(0)) ? (T)aNumD / aNumA : T(0);      // PCGStep3's guard (:544-547)
+                // r as received on the ring, then p = r + beta p everywhere: the bits of the pixel's owner
+#pragma unroll
+                for (int h = 0; h < HR; ++h) {
+                    const bool ownRow = h >= 1 && h <= R;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        if (!(ownRow && writer)) r[h].v[c] = ring[h].v[c];
+                        p[h].v[c] = moFma(betaB, p[h].v[c], r[h].v[c]);
+                    }
+                }
+                qPending = false; accQ = 0; phaseB = false;
+                continue;
+            }
+        }
         if constexpr (LM) {      // the q early-out of iteration k - 1 (solver.t:1093-1102): nothing of iteration k has been applied yet
-            if (!first) {
+            if (RESET ? qPending : !first) {
                 const T Q1 = (T)TOT[4];
                 const T zeta = T(k) * (Q1 - Q0) / Q1;
                 if (zeta < K.qTolerance) { if (K.lmBreak && blockIdx.x == 0 && tid == 0) { K.lmBreak[1] = (double)zeta; K.lmBreak[0] = (double)(k + 1); } break; }
@@ -289,6 +376,24 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
         const T beta = (aNum > T(0)) ? (T)bNumD / aNum : T(0);
         const bool last = k + 1 == K.L;
 
+        if constexpr (RESET) {
+            if (resetIt) {
+                // ---- PCGStep2_1stHalf (solverGPUGaussNewton.t:491-503): delta += alpha p, on the owned pixels and on the ring -------------------------------------------
+#pragma unroll
+                for (int h = 0; h < HR; ++h) {
+                    const bool ownRow = h >= 1 && h <= R;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        if (!ownRow) dr[h == 0 ? 0 : 1].v[c] = moFma(alpha, p[h].v[c], dr[h == 0 ? 0 : 1].v[c]);
+                        else if (DL_LDS) dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] = moFma(alpha, p[h].v[c], dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid]);
+                        else dl[!DL_LDS && ownRow ? h - 1 : 0].v[c] = moFma(alpha, p[h].v[c], dl[!DL_LDS && ownRow ? h - 1 : 0].v[c]);
+                    }
+                }
+                aNumA = aNum; phaseB = true;
+                continue;
+            }
+        }
+
         // ---- PCGStep2 + PCGStep3 (z = r): delta += alpha p;  r -= alpha A p;  p = r + beta p -- on the owned pixels and, with the same fused operations, on the ring
         accQ = 0;
 #pragma unroll
@@ -298,6 +403,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
             for (int c = 0; c < C; ++c) {
                 const T apv = ownRow ? (writer ? (AP_LDS ? apL[((AP_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] : ap[!AP_LDS && ownRow ? h - 1 : 0].v[c]) : ring[h].v[c]) : ring[h].v[c];
                 T dNew = 0;
+                if (RESET && !ownRow && !last) dr[RESET && h != 0 ? 1 : 0].v[c] = moFma(alpha, p[h].v[c], dr[RESET && h != 0 ? 1 : 0].v[c]);      // (the split residual reset applies A to delta)
                 if (ownRow) {
                     dNew = moFma(alpha, p[h].v[c], DL_LDS ? dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] : dl[!DL_LDS && ownRow ? h - 1 : 0].v[c]);
                     if (DL_LDS) dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] = dNew; else dl[!DL_LDS && ownRow ? h - 1 : 0].v[c] = dNew;
@@ -309,6 +415,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
                 }
             }
         }
+        if constexpr (RESET) qPending = !last;
     }
     if (failed && tid == 0 && K.hostErr) __hip_atomic_store(K.hostErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (!failed && writer) {
@@ -327,16 +434,16 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
 // ---- host side: the family's data for onchip_launch.h ----------------------------------------------------------------------------------------------------------
 constexpr OcFamily kMoFamily{kMoSpan, 2, kMoMaxG, kMoNWMax, "march_onchipPcg", "march_pcgIter", "generic kernels", nullptr};
 
-template <class T, class Op, int R, int WV, bool LM> constexpr size_t moLdsBytes() {      // A p and delta (where they wait in LDS) + b (LM) + the sums' staging
+template <class T, class Op, int R, int WV, int MODE> constexpr size_t moLdsBytes() {      // A p and delta (where they wait in LDS) + b (LM, both modes) + the sums' staging
     const size_t plane = (size_t)R * Op::C * sizeof(T) * WV * kWave;
     const bool apLds = Op::C * sizeof(T) * R >= 128, dlLds = apLds && Op::kCoef >= 4 && (Op::C + Op::kCoef) * sizeof(T) * R >= 256;
-    return (apLds ? plane : 0) + (dlLds ? plane : 0) + (LM ? plane : 0) + 12 * 1024;
+    return (apLds ? plane : 0) + (dlLds ? plane : 0) + (MODE != 0 ? plane : 0) + 12 * 1024;
 }
 // a variant whose registers do not hold its loop state is not instantiated (Op::spills, from the compiler's resource remarks); should a compiler upgrade make another one
 // spill it is still not offered (hipFuncGetAttributes): no scratch in a kernel that is all latency
-template <class T, class Op, int R, int WV, bool LM> const void* moKernel() {
-    if constexpr (moLdsBytes<T, Op, R, WV, LM>() <= 150 * 1024 && !Op::template spills<R, WV, LM>()) {
-        const void* fn = (const void*)march_onchipPcg<T, Op, R, WV, LM>;
+template <class T, class Op, int R, int WV, int MODE> const void* moKernel() {
+    if constexpr (moLdsBytes<T, Op, R, WV, MODE>() <= 150 * 1024 && !Op::template spills<R, WV, MODE>()) {
+        const void* fn = (const void*)march_onchipPcg<T, Op, R, WV, MODE>;
         hipFuncAttributes fa{};
         if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.localSizeBytes == 0) return fn;
         (void)hipGetLastError();
@@ -346,7 +453,7 @@ template <class T, class Op, int R, int WV, bool LM> const void* moKernel() {
 template <class T, class Op> const std::vector<OcVariant>& moVariants() {
     static const std::vector<OcVariant> v = [] {
         std::vector<OcVariant> o;
-#define MO_VARIANT(R, WV) o.push_back({R, WV, moKernel<T, Op, R, WV, false>(), moKernel<T, Op, R, WV, true>()})
+#define MO_VARIANT(R, WV) o.push_back({R, WV, moKernel<T, Op, R, WV, 0>(), moKernel<T, Op, R, WV, 1>(), moKernel<T, Op, R, WV, 2>()})
         MO_VARIANT(2, 4); MO_VARIANT(4, 4); MO_VARIANT(8, 4); MO_VARIANT(2, 8); MO_VARIANT(4, 8); MO_VARIANT(8, 8);
         if constexpr (Op::C * sizeof(T) <= 8) { MO_VARIANT(16, 4); MO_VARIANT(16, 8); }
 #undef MO_VARIANT
@@ -396,14 +503,14 @@ struct MarchOps : Base {
         produceCoefficients(ctx);
         return oc.solve(L, lm, delta, *this, ctx, [&](const OcGrant& g) {
             MoArgs<T> K{mW, mH, r0, p0, delta, marchFlags, coef, g.stripsX, g.tilesY, g.G, L, g.tag0, g.slots, g.box, g.bad, g.tmo.later, g.failAt, g.tmo.first, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0),
-                        g.hostErr, lm ? lm->breakInfo : nullptr};
+                        g.hostErr, lm ? lm->breakInfo : nullptr, lm ? lm->resetPeriod : 0};
             Op op = marchOp();
             void* kargs[] = {(void*)&op, (void*)&K};
             return g.launch(kargs, ctx.stream);
         });
     }
     OnchipGuard* onChipGuard() override { return &oc.guard; }
-    std::string describe(int L, bool lmv) override { return oc.describe(useMarch ? L : 0, lmv); }
+    std::string describe(int L, bool lmv, const OnChipLm<T>* lmc) override { return oc.describe(useMarch ? L : 0, lmv, lmc); }
 };
 
 }  // namespace

@@ -75,7 +75,7 @@ double OptAmd_PlanTrustRegionRadius(Opt_Plan* plan);
 /* Which linear-solve path the plan's last step took:
  *   0  launch-per-iteration kernels (the problem does not fit the chip, the kernel set has no on-chip solve, it is switched off: "amd_onchip" = 0 / "amd_reference_order",
  *      or a Levenberg-Marquardt solve passes a residual reset -- lIterations > residual_reset_period -- on a kernel set that keeps such a solve on chip only with
- *      "amd_onchip" = 2);
+ *      "amd_onchip" = 2 (the 5-point stencils) / 3 (shape_from_shading));
  *   1  the whole linear solve of the last step ran as one persistent on-chip launch;
  *   2  the plan is in its back-off after a failed on-chip launch: the waits of a launch's first phase are bounded by 10 ms (passing them proves the whole grid resident;
  *      a foreign tenant holding CUs makes the launch give up there, before anything has been written), the step was redone by the streaming kernels (reported on stderr the
@@ -99,7 +99,8 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          on chip when a residual reset falls inside it (lIterations > residual_reset_period > 0): the reference's split PCGStep2
  *                          (solverGPUGaussNewton.t:1077-1086) runs inside the launch.  The reference's own callers sit there (poisson_image_editing: 100 linear iterations,
  *                          optical_flow: 50, period 10).  It is opt-in because the two paths round differently (see OptAmd_PlanOnChipStatus).  image_warping resets on chip
- *                          under 1 and 2 alike; shape_from_shading keeps such a solve on the launch-per-iteration loop under both.
+ *                          under every value but 0; shape_from_shading keeps such a solve on the launch-per-iteration loop under 1 and 2.  3: as 2, and shape_from_shading
+ *                          too (sfs_onchipPcg's third mode; the reference's own caller runs lIterations = 10 with the period at 10, so only longer solves get here).
  * OptAmd_PlanDescribe reports the choice.  (The environment switches OPT_AMD_ONEKERNEL / OPT_AMD_ONCHIP remain as process-wide development overrides.) */
 
 /* The float4 copy rate of this box in GB/s: `bytes` moved in total per repetition (half read, half written; device memory allocated and freed inside the call),

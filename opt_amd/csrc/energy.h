@@ -103,7 +103,7 @@ struct LmInitArgs {
 // Levenberg-Marquardt controls of EnergyOps::pcgSolveOnChip: the scalars of PCGFinalizeDiagonal (solver.t:631-664), q_tolerance and residual_reset_period (:1077-1102).
 template <class T>
 struct OnChipLm { T radius, minLm, maxLm, qTolerance; int resetPeriod; const T* CtC = nullptr;
-                  int onchip = 1;                  // the plan's amd_onchip: 2 = a residual reset inside the solve (resetPeriod < lIterations) may stay on chip where the kernel family has that mode
+                  int onchip = 1;                  // the plan's amd_onchip: a residual reset inside the solve (resetPeriod < lIterations) may stay on chip from 2 on (5-point stencils) / from 3 on (shape_from_shading too)
                   double* breakInfo = nullptr; };      // pinned, 2 doubles: workgroup 0 leaves {iteration of the q early-out + 1, zeta} there (0: the loop ran to its end) -- the solver prints the
                                                        // reference's "breaking at iteration" message from it when someone listens (verbosity > 0)      // CtC: the clamped diagonal PCGFinalizeDiagonal has just written (energies whose kernel does not rebuild it from a table)
 

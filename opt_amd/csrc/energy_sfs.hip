@@ -639,7 +639,7 @@ struct SfsOps : EnergyOps<T> {
         // Which variant, if any: among those whose workgroups fit one per CU, the one with the fewest marching trips per SIMD and iteration -- (waves per SIMD) x (rows
         // held per wave).  The buffers are sized for the plan's image when the plan is made.
         oc.init(OcFamily{kSoSpan, 4, kSoMaxG, kSoNW, "sfs_onchipPcg", "sfs_pcgMarch", "sfs_pcgMarch",
-                         "Opt(amd): the on-chip shape_from_shading kernel (%d rows, %d waves) could not be launched; the plan stays on the marching kernels\n"},
+                         "Opt(amd): the on-chip shape_from_shading kernel (%d rows, %d waves) could not be launched; the plan stays on the marching kernels\n", 3},
                 soVariantList, A.W, A.H, 1, cus, std::min<long>(kMaxPartials, cus * 8L));
         oc.reserve();
 #if SO_PROFILE
@@ -759,10 +759,19 @@ struct SfsOps : EnergyOps<T> {
     OnchipLauncher<T> oc;
     OnchipGuard* onChipGuard() override { return &oc.guard; }
     long long* soProf = nullptr;
+    // MODE 2 (LM with the residual reset inside the solve): the compiler's resource remarks show no scratch in any of the sixteen (double, 10 rows, 8 waves keeps delta of
+    // its ring rows in LDS); should a compiler upgrade make one spill it is not offered (hipFuncGetAttributes): no scratch in a kernel that is all latency
+    template <int R, int WV> static const void* soResetKernel() {
+        const void* fn = (const void*)sfs_onchipPcg<T, R, 2, WV>;
+        hipFuncAttributes fa{};
+        if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.localSizeBytes == 0) return fn;
+        (void)hipGetLastError();
+        return nullptr;
+    }
     static const std::vector<OcVariant>& soVariantList() {
         static const std::vector<OcVariant> v = [] {
             std::vector<OcVariant> o;
-#define SO_VARIANT(R, WV) o.push_back({R, WV, (const void*)sfs_onchipPcg<T, R, false, WV>, (const void*)sfs_onchipPcg<T, R, true, WV>})
+#define SO_VARIANT(R, WV) o.push_back({R, WV, (const void*)sfs_onchipPcg<T, R, 0, WV>, (const void*)sfs_onchipPcg<T, R, 1, WV>, soResetKernel<R, WV>()})
             SO_VARIANT(4, 4); SO_VARIANT(6, 4); SO_VARIANT(8, 4); SO_VARIANT(10, 4);
             SO_VARIANT(4, 8); SO_VARIANT(6, 8); SO_VARIANT(8, 8); SO_VARIANT(10, 8);
 #undef SO_VARIANT
@@ -774,7 +783,7 @@ struct SfsOps : EnergyOps<T> {
         if (this->slab.active || traceDev) return false;
         return oc.solve(L, lmArgs, delta, *this, ctx, [&](const OcGrant& g) {
             SfsOcArgs<T> K{A, r0, p0, lmArgs ? lmArgs->CtC : nullptr, delta, g.stripsX, g.tilesY, g.G, L, g.tag0, g.slots, g.box, g.bad, g.tmo.later, g.failAt, g.tmo.first, lmArgs ? lmArgs->qTolerance : T(0),
-                           g.hostErr, soProf, lmArgs ? lmArgs->breakInfo : nullptr};
+                           g.hostErr, soProf, lmArgs ? lmArgs->breakInfo : nullptr, lmArgs ? lmArgs->resetPeriod : 0};
             void* kargs[] = {(void*)&K};
             if (!g.launch(kargs, ctx.stream)) return false;
 #if SO_PROFILE

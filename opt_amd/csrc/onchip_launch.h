@@ -18,6 +18,7 @@ struct OcFamily {
     int span, halo, maxG, words;             // pixels a wave owns per row; rows it holds around its own (the cost model); workgroup cap; tagged words per workgroup
     const char *kernel, *loopGN, *loopLM;    // describe(): the kernel, the launch-per-iteration loops it stands in for
     const char* launchFailed;                // stderr text (rows, waves) when the launch itself is refused, or nullptr: silent
+    int resetFrom = 2;                       // the amd_onchip value from which the family keeps a residual reset inside the solve on chip (5-point stencils: 2, shape_from_shading: 3)
 };
 struct OcPlan {
     const OcVariant* V = nullptr; int stripsX = 0, tilesY = 0, G = 0;
@@ -56,7 +57,7 @@ struct OnchipLauncher {
         return best;
     }
     // THE predicate: would a linear solve of L iterations run on chip, and with which variant?  lmv: the Levenberg-Marquardt loop (lm: its controls, where the caller has
-    // them).  A split residual reset before the last iteration (residual_reset_period < L) takes the family's mode-2 kernel, for a caller who opted in (amd_onchip = 2)
+    // them).  A split residual reset before the last iteration (residual_reset_period < L) takes the family's mode-2 kernel, for a caller who opted in (amd_onchip >= OcFamily::resetFrom)
     // and where such a variant fits; otherwise it is the launch-per-iteration loop's business.  solve(), describe(), reserve() and a kernel set that wants to know before
     // it spends a coefficient pass all ask here.
     bool resetInside(int L, const OnChipLm<T>* lm) const { return lm && lm->resetPeriod < L; }
@@ -65,7 +66,7 @@ struct OnchipLauncher {
         if (!guard.usable() || L <= 0 || (unsigned long long)W * H * C * sizeof(T) >= (1ull << 30)) return {};
         if (lm && !lm->CtC) return {};
         if (!resetInside(L, lm)) { OcPlan P = select(lmv ? 1 : 0); P.phases = L; return P; }
-        if (lm->onchip < 2 || lm->resetPeriod <= 0) return {};
+        if (lm->onchip < fam.resetFrom || lm->resetPeriod <= 0) return {};
         OcPlan P = select(2);
         P.phases = L + (L - 1) / lm->resetPeriod;
         return P;
@@ -111,7 +112,8 @@ struct OnchipLauncher {
     std::string describe(int L, bool lmv, const OnChipLm<T>* lm, const char* blocked = nullptr) const {
         const OcPlan P = blocked ? OcPlan{} : plan(L, lmv, lm);
         const bool reset = resetInside(L, lm);
-        char buf[700];
+        char buf[700], optIn[160];
+        snprintf(optIn, sizeof optIn, "a residual reset falls inside the solve (lIterations > residual_reset_period) and amd_onchip=%d was not set", fam.resetFrom);
         if (P) snprintf(buf, sizeof buf, "path=on-chip (%s%s); onchip_rows_per_wave=%d; waves_per_workgroup=%d; wave_tiles=%dx%d of %d x %d pixels; workgroups=%d of %d CUs; fallback=one launch per PCG iteration (%s)",
                         fam.kernel, !lmv ? "" : P.mode == 2 ? ", LM with the residual resets inside the solve" : ", LM, no residual reset inside the solve", P.V->rows, P.V->waves, P.stripsX, P.tilesY, fam.span,
                         P.V->rows, P.G, cus, lmv ? fam.loopLM : fam.loopGN);
@@ -120,7 +122,7 @@ struct OnchipLauncher {
                       : !reset || !select(1) ? "the wave tiles do not fit the CUs"
                       : !offersReset() ? "a residual reset falls inside the solve (lIterations > residual_reset_period) and this kernel family has no on-chip reset"
                       : lm->resetPeriod <= 0 ? "residual_reset_period <= 0"
-                      : lm->onchip < 2 ? "a residual reset falls inside the solve (lIterations > residual_reset_period) and amd_onchip=2 was not set"
+                      : lm->onchip < fam.resetFrom ? optIn
                       : "a residual reset falls inside the solve and no variant with the reset on chip fits the CUs");
         return buf;
     }

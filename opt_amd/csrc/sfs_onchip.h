@@ -17,10 +17,17 @@
 //           (solver.t:1093-1102) agree on the whole grid without a broadcast.  One grid-wide wait per iteration.
 // Levenberg-Marquardt: + CtC p (o.t:2076-2082); Q_k = 1/2 sum delta . (r + b) (:483-485) is formed where iteration k is applied and travels with the sums of
 // iteration k + 1 -- exactly the hand-over of the launch-per-iteration loop (solver.hip runLaunchPerIterationLM), so an early-out leaves the reference's delta.
-// A split residual reset in the MIDDLE of a linear solve (lIterations > residual_reset_period) is not offered: the host keeps such solves on sfs_pcgMarch.
+// A split residual reset in the MIDDLE of a linear solve (lIterations > residual_reset_period) keeps the solve on sfs_pcgMarch by default; with the solver parameter
+// amd_onchip = 3 it takes the kernel's third mode (MODE 2: stencil_onchip.h's protocol, re-cut for the two-pixel ring).  An iteration k with (k + 1) % residual_reset_period == 0,
+// k + 1 < L takes two trips through the loop, one per grid-wide wait: phase A as ever up to delta += alpha p (PCGStep2_1stHalf; the ring's A p is neither posted nor awaited),
+// then phase B -- the SAME march over delta instead of p (computeAdelta + PCGStep2_2ndHalf, solverGPUGaussNewton.t:1077-1086): r = b - (J^T J + CtC) delta, z = r, sum r.r
+// (beta's numerator) and Q in the sums, the new r of the tile's two outermost rows / columns in the words A p takes otherwise; the zeta test of that iteration is taken right
+// there.  The wave also keeps delta of its four ring rows.  Phases, not iterations, number the tags and pick the parity.
+// In float the march of MODE 2 runs its arithmetic in double on the float operands (type M below): r = b - A delta cancels, so A delta is rounded once, not per term.
 // Every wait is bounded by the device's wall clock; a time-out raises `bad`, every workgroup leaves the loop at its next sum, nothing is written to delta and the
 // host redoes the linear solve with the marching kernels.  The grid must be co-resident (one workgroup per CU): the launcher checks workgroups <= CUs.
 #pragma once
+#include <type_traits>
 #include "onchip_launch.h"
 
 namespace optamd {
@@ -47,6 +54,7 @@ struct SfsOcArgs {
     int* hostErr;                       // LM (the solver applies the update itself): pinned host word a workgroup that gave up raises on its way out; GN: nullptr (ocApplyDelta tells the host)
     long long* prof;                    // SO_PROFILE builds: [G][8] ticks per phase (wave 0 of every workgroup), else nullptr
     double* lmBreak;                    // pinned {iteration + 1, zeta} of the q early-out (OnChipLm::breakInfo), or nullptr
+    int resetPeriod;                    // MODE 2: every resetPeriod-th iteration (but the last) ends with the split residual reset
 };
 
 // Development builds (opt_amd/build.py build_variant with SO_PROFILE=1; OPT_AMD_ONCHIP_PROFILE=1): thread 0 of every workgroup accumulates the wall-clock ticks
@@ -68,8 +76,13 @@ __device__ __forceinline__ double soFma(double a, double b, double c) { return _
 
 // WAVES: waves per workgroup = per CU (4: one per SIMD, 8: two).  A marching trip is ~350 instructions whatever the row holds, so an iteration costs
 // (waves per SIMD) x (R + 4) trips: the launcher picks the (R, WAVES) that minimises it among those whose workgroups fit one per CU.
-template <class T, int R, bool LM, int WAVES>
+// MODE: 0 Gauss-Newton, 1 Levenberg-Marquardt, 2 Levenberg-Marquardt with the split residual reset inside the solve
+template <class T, int R, int MODE, int WAVES>
 __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
+    constexpr bool LM = MODE != 0, RESET = MODE == 2;
+    // The march's arithmetic type.  MODE 2 in float forms A p and A delta in double from the float operands and rounds once: r = b - A delta cancels to a small r, so the
+    // rounding of A delta would enter r whole, at the size of b (the other modes and double: the solver's precision, as ever).
+    using M = std::conditional_t<RESET && sizeof(T) == 4, double, T>;
     constexpr int kSoWaves = WAVES, kSoBlock = WAVES * kWave;
     constexpr int HR = R + 4;                          // held rows: two above and two below the R owned ones
     constexpr int WPS = (int)sizeof(T) / 4;            // tagged words per scalar
@@ -86,6 +99,8 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
     __shared__ T apL[(AP_LDS ? R : 1) * kSoBlock];
     constexpr bool DL_LDS = sizeof(T) * R >= 80 && WAVES == 8;      // ... and delta itself in the tightest variant (double, R = 10, two waves per SIMD: 1024^2)
     __shared__ T dlL[(DL_LDS ? R : 1) * kSoBlock];
+    constexpr bool DR_LDS = RESET && DL_LDS;                        // MODE 2: ... and delta of the four ring rows
+    __shared__ T drL[(DR_LDS ? 4 : 1) * kSoBlock];
     const SArgs<T>& A = K.A;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = blockIdx.x;      // (wave: uniform, kept in a scalar register)
     const int tile = g * kSoWaves + wave;
@@ -145,106 +160,131 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
     double accQ = 0;
     T Q0 = 0;                                  // fetchQ before the loop (solver.t:1050): delta = 0, so exactly 0
     const size_t boxStride = (size_t)N * WPS;
+    // RESET.  State: delta of the ring rows above and below the tile (held rows 0, 1, R + 2, R + 3; the ring columns' delta in the owned rows is dl of lanes 0, 1, 62, 63: every
+    // lane applies delta += alpha p to the R pixels of its column), the phases passed so far, whether this trip is a phase B, the alpha numerator of its phase A, and whether
+    // the Q of the iteration before travels with this trip's sums (after a reset it has been tested).
+    T dr[RESET && !DR_LDS ? 4 : 1];
+    if constexpr (RESET) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { if (DR_LDS) drL[(DR_LDS ? j : 0) * kSoBlock + tid] = 0; else dr[DR_LDS ? 0 : j] = 0; }
+    }
+    // delta of held row h (compile-time h)
+    auto deltaRow = [&](int h) -> T {
+        if (h >= 2 && h < R + 2) return DL_LDS ? dlL[(DL_LDS ? h - 2 : 0) * kSoBlock + tid] : dl[DL_LDS ? 0 : h - 2];
+        const int j = h < 2 ? h : h - R;
+        return DR_LDS ? drL[(DR_LDS ? j : 0) * kSoBlock + tid] : dr[RESET && !DR_LDS ? j : 0];
+    };
+    auto ringDeltaAdd = [&](int h, T alpha) {      // delta += alpha p of a ring row
+        const int j = h < 2 ? h : h - R;
+        if (DR_LDS) drL[(DR_LDS ? j : 0) * kSoBlock + tid] = soFma(alpha, p[h], drL[(DR_LDS ? j : 0) * kSoBlock + tid]);
+        else dr[RESET && !DR_LDS ? j : 0] = soFma(alpha, p[h], dr[RESET && !DR_LDS ? j : 0]);
+    };
+    unsigned phase = 0;
+    bool phaseB = false, qPending = false;
+    T aNumA = 0;
 
 #if SO_PROFILE
     long long soProf[8] = {0, 0, 0, 0, 0, 0, 0, 0}, soPrev = wall_clock64();
 #endif
-    for (int k = 0; k < K.L; ++k) {
+    for (int k = 0; k < K.L; k += (RESET && phaseB) ? 0 : 1) {
         // What is derived from the tile's position (row addresses of six arrays, bounds predicates) is invariant over the solve; hoisted out of this loop it would occupy
         // a hundred registers.  The empty asm makes the sources opaque per iteration, so each use recomputes its two or three instructions.
         asm volatile("" : "+v"(pixBase), "+v"(xc), "+s"(yBase));
-        const unsigned tag = K.tag0 + (unsigned)k;
+        const unsigned tag = K.tag0 + (RESET ? phase : (unsigned)k);
         const int par = (int)(tag & 1u);
         oc_u64* const box = K.apBox + (size_t)par * boxStride;
         oc_u64* const slotPar = K.slots + (size_t)par * K.G * kSoNW;
         if (k == K.failAt && g == 0 && tid == 0) __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const bool first = k == 0;
+        const bool resetIt = RESET && k + 1 < K.L && (k + 1) % K.resetPeriod == 0;      // this iteration ends with the split residual reset: r is formed anew, nobody needs the ring's A p
+        const bool inB = RESET && phaseB;      // this trip is the reset's second half: the march runs over delta
 
         // ---- PCGStep1: A p_k on the owned pixels, with the sums (the expressions of sfs_pcgMarch, in its order) ------------------------------------------------
         double acc = 0, accNum = 0, acc2 = 0, acc3 = 0, accX = 0;
         if (!idle) {
-            SoRow<T> R1{}, R2{}, R3{};
-            SQ<T> q2{}, q3{};
-            T b1 = 0, cy1 = 0, cy2 = 0;
-            T ctcQ[2] = {0, 0};      // CtC of the owned rows: requested when the row is staged, used two trips later by its gather
+            SoRow<M> R1{}, R2{}, R3{};
+            SQ<M> q2{}, q3{};
+            M b1 = 0, cy1 = 0, cy2 = 0;
+            M ctcQ[2] = {0, 0};      // CtC of the owned rows: requested when the row is staged, used two trips later by its gather
 #pragma unroll
             for (int h = 0; h < HR; ++h) {
                 asm volatile("" : "+s"(yBase), "+v"(xc));      // (per trip: the row predicates and addresses of all trips are otherwise formed at the top of the iteration and kept -- in scalar registers the kernel does not have)
                 const SoRowC<T> c = cq[h % kSoDepth];
-                const T ctcNow = ctcQ[h % 2];
+                const M ctcNow = ctcQ[h % 2];
                 if (LM && h >= 2 && h < R + 2) ctcQ[h % 2] = ctcp[rowIdx(h)];
                 cq[h % kSoDepth] = loadRow((h + kSoDepth) % HR);      // (behind the last rows: rows 0 .. kSoDepth - 1 of the next iteration)
                 const int Y = yBase - 2 + h;
                 // The staged row.  The masks of sfs_pcgMarch -- `interior row centre ? w_g * edge mask : 0`, `regularisation rows on ? w_s : 0` -- are formed ONCE per
                 // pixel as multipliers in the solver's precision and travel to the neighbouring columns as such: where the march selects `ok ? m * g : 0` per use, this
                 // kernel multiplies by a multiplier that is exactly 0 -- the same products in the same order where the row counts, +-0 where it does not.
-                SoRow<T> n;
+                SoRow<M> n;
                 {
                     const bool in = rowIn(h);
                     n.v = p[h]; n.rk = r[h];
+                    if constexpr (RESET) { if (inB) n.v = deltaRow(h); }
                     // (the gradient images of a pixel outside the image are whatever the clamped address holds -- finite numbers: they only ever meet a p or a multiplier
                     //  that is exactly 0 there, or end in an output that the `excluded` test below zeroes)
                     n.g0 = c.g0; n.g1 = c.g1; n.g2 = c.g2;
                     const bool ok = in && sfs_interior(A, x, Y);
-                    n.wr = ok ? wG * (T)sfsMr(c.fb) : T(0); n.wc = ok ? wG * (T)sfsMc(c.fb) : T(0);
-                    n.ws = (ok && (c.fb & kSfsValid)) ? wS : T(0);
+                    n.wr = ok ? wG * (M)sfsMr(c.fb) : M(0); n.wc = ok ? wG * (M)sfsMc(c.fb) : M(0);
+                    n.ws = (ok && (c.fb & kSfsValid)) ? wS : M(0);
                     n.ex = in ? (c.fb & kSfsEx) : 0;
                 }
-                const T cyN = uniLane(cyLane, h);
+                const M cyN = uniLane(cyLane, h);
                 // b(., Y) = g1 v + g0 v(x-1) + g2 v(y-1)                                      (d B_I(c) . v)
-                const T vL = dppShift<true>(n.v);
-                const T bY = n.g1 * n.v + n.g0 * vL + n.g2 * R1.v;
+                const M vL = dppShift<true>(n.v);
+                const M bY = n.g1 * n.v + n.g0 * vL + n.g2 * R1.v;
                 // row values at the centres of row Y - 1 (R1); those of the held rows 0 and 1 feed no owned pixel
-                SQ<T> qn{};
+                SQ<M> qn{};
                 if (h >= 2) {
-                    const T right = dppShift<false>(b1);
+                    const M right = dppShift<false>(b1);
                     qn.gh = R1.wr * (b1 - right);
                     qn.gv = R1.wc * (b1 - bY);
-                    const T v1l = dppShift<true>(R1.v), v1r = dppShift<false>(R1.v);
-                    T js[3];
+                    const M v1l = dppShift<true>(R1.v), v1r = dppShift<false>(R1.v);
+                    M js[3];
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
-                        const T c0 = q == 0 ? cxc : q == 1 ? cy1 : T(1), cl = q == 0 ? cxl : q == 1 ? cy1 : T(1), cu = q == 0 ? cxc : q == 1 ? cy2 : T(1),
-                                cr = q == 0 ? cxr : q == 1 ? cy1 : T(1), cd = q == 0 ? cxc : q == 1 ? cyN : T(1);
-                        T sj = 0;
-                        sj += (T(4) * c0) * R1.v; sj += (T(-1) * cl) * v1l; sj += (T(-1) * cu) * R2.v; sj += (T(-1) * cr) * v1r; sj += (T(-1) * cd) * n.v;
+                        const M c0 = q == 0 ? cxc : q == 1 ? cy1 : M(1), cl = q == 0 ? cxl : q == 1 ? cy1 : M(1), cu = q == 0 ? cxc : q == 1 ? cy2 : M(1),
+                                cr = q == 0 ? cxr : q == 1 ? cy1 : M(1), cd = q == 0 ? cxc : q == 1 ? cyN : M(1);
+                        M sj = 0;
+                        sj += (M(4) * c0) * R1.v; sj += (M(-1) * cl) * v1l; sj += (M(-1) * cu) * R2.v; sj += (M(-1) * cr) * v1r; sj += (M(-1) * cd) * n.v;
                         js[q] = R1.ws * sj;
                     }
                     qn.s0 = js[0]; qn.s1 = js[1]; qn.s2 = js[2];
                 }
                 // gather of row y = Y - 2 (centre row R2; row values qn at y + 1, q2 at y, q3 at y - 1): held row h - 2, owned row h - 4
                 if (h >= 4) {
-                    const T ve = R2.v;
-                    T s = 0;
-                    auto add = [&](T coef, T q) { s += coef * q; };
+                    const M ve = R2.v;
+                    M s = 0;
+                    auto add = [&](M coef, M q) { s += coef * q; };
                     add(wP, wP * ve);      // the fitting row
                     // The rows centred on the pixel itself and on the pixels above / below: as in the march.  The rows centred on the LEFT and RIGHT neighbours are summed by
                     // those lanes -- from their own row values and multipliers, the output pixel's dB_I / P coefficient fetched from it -- and arrive as ONE shifted partial
                     // sum per side: 5 whole-wave shifts instead of 19 (the march shifts every operand).  Same products, another association of the sum.
-                    const T g0r = dppShift<false>(R2.g0);
+                    const M g0r = dppShift<false>(R2.g0);
                     add(R2.wr * (R2.g1 - g0r), q2.gh);                     // gh, centre (x, y)
                     add(R1.wr * R1.g2, qn.gh);                             // (x, y+1)
                     add(R2.wc * (R2.g1 - R1.g2), q2.gv);                   // gv, centre (x, y)
                     add(R1.wc * R1.g2, qn.gv);                             // (x, y+1)
                     add(-(R3.wc * R2.g1), q3.gv);                          // (x, y-1)
-                    T sReg = 0;      // (the regularisation rows of the column in a chain of their own: four independent chains per pixel instead of one of 26 dependent operations)
-                    auto reg = [&](T ws, T w4, T a0, T a1, T a2) {
-                        const T wgt = ws * w4;
-                        sReg += (wgt * cxc) * a0; sReg += (wgt * cy2) * a1; sReg += (wgt * T(1)) * a2;
+                    M sReg = 0;      // (the regularisation rows of the column in a chain of their own: four independent chains per pixel instead of one of 26 dependent operations)
+                    auto reg = [&](M ws, M w4, M a0, M a1, M a2) {
+                        const M wgt = ws * w4;
+                        sReg += (wgt * cxc) * a0; sReg += (wgt * cy2) * a1; sReg += (wgt * M(1)) * a2;
                     };
-                    reg(R2.ws, T(4), q2.s0, q2.s1, q2.s2);
-                    reg(R1.ws, T(-1), qn.s0, qn.s1, qn.s2);
-                    reg(R3.ws, T(-1), q3.s0, q3.s1, q3.s2);
+                    reg(R2.ws, M(4), q2.s0, q2.s1, q2.s2);
+                    reg(R1.ws, M(-1), qn.s0, qn.s1, qn.s2);
+                    reg(R3.ws, M(-1), q3.s0, q3.s1, q3.s2);
                     s += sReg;
                     {
-                        const T wgt = R2.ws * T(-1), wy = wgt * cy2, w1 = wgt * T(1);
+                        const M wgt = R2.ws * M(-1), wy = wgt * cy2, w1 = wgt * M(1);
                         // for the pixel on the LEFT, whose right-hand neighbour this lane is: rows (x+1, y), (x+1, y-1) of its gather
-                        T tR = 0;
+                        M tR = 0;
                         tR += (R2.wr * R2.g0) * q2.gh; tR += (R2.wc * R2.g0) * q2.gv; tR += -(R3.wc * R2.g0) * q3.gv;
                         tR += (wgt * cxl) * q2.s0; tR += wy * q2.s1; tR += w1 * q2.s2;
                         // for the pixel on the RIGHT: rows (x-1, y), (x-1, y+1) of its gather (its own dB_I / d d1 at rows y, d d2 at row y + 1 multiply them)
-                        const T g1R = dppShift<false>(R2.g1), g2R1 = dppShift<false>(R1.g2);
-                        T tL = 0;
+                        const M g1R = dppShift<false>(R2.g1), g2R1 = dppShift<false>(R1.g2);
+                        M tL = 0;
                         tL += -(R2.wr * g1R) * q2.gh; tL += -(R1.wr * g2R1) * qn.gh;
                         tL += (wgt * cxr) * q2.s0; tL += wy * q2.s1; tL += w1 * q2.s2;
                         s += dppShift<false>(tR);
@@ -252,18 +292,29 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
                     }
                     if (LM) s += ctcNow * ve;
                     if (!R2.ex) s = 0;
-                    if (AP_LDS) apL[(AP_LDS && h >= 4 ? h - 4 : 0) * kSoBlock + tid] = s; else apOwn[!AP_LDS && h >= 4 ? h - 4 : 0] = s;
+                    const T sT = (T)s;      // (A p as it is applied and posted: the solver's precision)
+                    if (!inB) { if (AP_LDS) apL[(AP_LDS && h >= 4 ? h - 4 : 0) * kSoBlock + tid] = sT; else apOwn[!AP_LDS && h >= 4 ? h - 4 : 0] = sT; }
                     if (writer && Y - 2 < A.H) {
-                        acc += (double)(ve * s);
-                        const T rk = R2.rk;
-                        const T zk = first ? ve : rk;                                          // iteration 0: alphaNumerator_0 = r_0 . p_0 (the reference's start)
-                        accNum += (double)(zk * rk); acc2 += (double)(rk * s); acc3 += (double)(s * s);
-                        if (first) accX += (double)(rk * rk);
-                        // the tile's two outermost rows / columns: to the tagged image, for whoever holds them as ring
-                        if (h - 4 < 2 || h - 4 >= R - 2 || lane < 4 || lane >= kWave - 4) {
+                        T post = sT;
+                        if (inB) {      // phase B: r = b - (J^T J + CtC) delta, z = r; sum r.r in the alpha-numerator slot, Q (solver.t:483-485) in the fifth
+                            const T bv = bL[(LM && h >= 4 ? h - 4 : 0) * kSoBlock + tid];
+                            const T rn = (T)((M)bv - s);      // one rounding of the difference
+                            r[h >= 4 ? h - 2 : 0] = rn;
+                            accNum += (double)(rn * rn);
+                            accX += (double)(M(0.5) * (ve * ((M)rn + (M)bv)));
+                            post = rn;
+                        } else {
+                            acc += (double)(ve * (M)sT);
+                            const M rk = R2.rk;
+                            const M zk = first ? ve : rk;                                          // iteration 0: alphaNumerator_0 = r_0 . p_0 (the reference's start)
+                            accNum += (double)(zk * rk); acc2 += (double)(rk * (M)sT); acc3 += (double)((M)sT * (M)sT);
+                            if (first) accX += (double)(rk * rk);
+                        }
+                        // the tile's two outermost rows / columns: to the tagged image, for whoever holds them as ring (phase B: the new r; phase A of a reset: nobody waits for them)
+                        if ((inB || !resetIt) && (h - 4 < 2 || h - 4 >= R - 2 || lane < 4 || lane >= kWave - 4)) {
                             const int i = pixBase + (h - 2) * A.W;
-                            if constexpr (WPS == 1) ocStore(box + i, tag, __float_as_uint((float)s));
-                            else { const oc_u64 b = (oc_u64)__double_as_longlong((double)s); ocStore(box + 2 * (size_t)i, tag, (unsigned)b); ocStore(box + 2 * (size_t)i + 1, tag, (unsigned)(b >> 32)); }
+                            if constexpr (WPS == 1) ocStore(box + i, tag, __float_as_uint((float)post));
+                            else { const oc_u64 b = (oc_u64)__double_as_longlong((double)post); ocStore(box + 2 * (size_t)i, tag, (unsigned)b); ocStore(box + 2 * (size_t)i + 1, tag, (unsigned)(b >> 32)); }
                         }
                     }
                 }
@@ -272,7 +323,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
             }
         }
         SO_MARK(0);      // march
-        if (!first) accX = accQ;      // Q of the iteration before (LM; 0 otherwise)
+        if (!first && !inB) accX = accQ;      // Q of the iteration before (LM; 0 otherwise)
         asm volatile("" : "+v"(pixBase), "+v"(xc), "+s"(yBase));      // (the row predicates of the march are not kept for the wait: recomputed there)
 
         // ---- the grid-wide sums; the ring's A p is collected inside the wait ------------------------------------------------------------------------------------
@@ -299,7 +350,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
             constexpr int kPer = (kSoMaxG * kSoNW + kSoBlock - 1) / kSoBlock;
             oc_u64 w[kPer];
             const int nW = K.G * kSoNW;
-            const bool lastIt = k + 1 == K.L;      // (after the last iteration only delta survives: nobody needs the ring)
+            const bool lastIt = k + 1 == K.L || (resetIt && !inB);      // (after the last iteration only delta survives: nobody needs the ring; nor in front of a reset)
             auto need = [&](int h) { return !lastIt && rowIn(h) && !(writer && h >= 2 && h < R + 2); };
             oc_u64 rw[HR][WPS];
             bool sumsOk = false, ringOk = false;
@@ -359,7 +410,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
                     if (check()) break;
                     if ((++spins & 31u) == 0) {
                         if (__hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-                        if (wall_clock64() - t0 > (k == 0 ? K.firstTicks : to)) { __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                        if (wall_clock64() - t0 > (k == 0 && !inB ? K.firstTicks : to)) { __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                     }
                 }
             }
@@ -395,7 +446,29 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
         SO_MARK(4);      // sum over workgroups
         const double aNumD = TOT[0], aDenD = TOT[1], s2 = TOT[2], s3 = TOT[3], xD = TOT[4];
         if (reinterpret_cast<const int*>(TOT + kSoNS)[0]) { failed = true; break; }      // uniform over the workgroup: a wait timed out somewhere
-        if (LM && !first) {      // the q early-out of iteration k - 1 (solver.t:1093-1102): nothing of iteration k has been applied yet
+        if constexpr (RESET) {
+            ++phase;
+            if (phaseB) {
+                {      // the q test of THIS iteration: the split step delivers Q directly
+                    const T Q1 = (T)xD;
+                    const T zeta = T(k + 1) * (Q1 - Q0) / Q1;
+                    if (zeta < K.qTolerance) { if (K.lmBreak && blockIdx.x == 0 && tid == 0) { K.lmBreak[1] = (double)zeta; K.lmBreak[0] = (double)(k + 2); } break; }
+                    Q0 = Q1;
+                }
+                const T betaB = (aNumA > T(0)) ? (T)aNumD / aNumA : T(0);      // PCGStep3's guard (:544-547)
+                // r as received on the ring, then p = r + beta p everywhere: the bits of the pixel's owner
+#pragma unroll
+                for (int h = 0; h < HR; ++h) {
+                    const bool ownRow = h >= 2 && h < R + 2;
+                    if (!(ownRow && writer)) r[h] = ring[h];
+                    p[h] = soFma(betaB, p[h], r[h]);
+                }
+                qPending = false; accQ = 0; phaseB = false;
+                SO_MARK(5);
+                continue;
+            }
+        }
+        if (LM && (RESET ? qPending : !first)) {      // the q early-out of iteration k - 1 (solver.t:1093-1102): nothing of iteration k has been applied yet
             const T Q1 = (T)xD;
             const T zeta = T(k) * (Q1 - Q0) / Q1;
             if (zeta < K.qTolerance) { if (K.lmBreak && blockIdx.x == 0 && tid == 0) { K.lmBreak[1] = (double)zeta; K.lmBreak[0] = (double)(k + 1); } break; }
@@ -409,6 +482,22 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
         const T beta = (aNum > T(0)) ? (T)bNumD / aNum : T(0);
         const bool last = k + 1 == K.L;
 
+        if constexpr (RESET) {
+            if (resetIt) {
+                // ---- PCGStep2_1stHalf (solverGPUGaussNewton.t:491-503): delta += alpha p, on the owned pixels and on the ring -------------------------------------------
+#pragma unroll
+                for (int h = 0; h < HR; ++h) {
+                    const bool ownRow = h >= 2 && h < R + 2;
+                    if (!ownRow) ringDeltaAdd(h, alpha);
+                    else if (DL_LDS) dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] = soFma(alpha, p[h], dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid]);
+                    else dl[!DL_LDS && ownRow ? h - 2 : 0] = soFma(alpha, p[h], dl[!DL_LDS && ownRow ? h - 2 : 0]);
+                }
+                aNumA = aNum; phaseB = true;
+                SO_MARK(5);
+                continue;
+            }
+        }
+
         // ---- PCGStep2 + PCGStep3 (z = r: this energy does not precondition after the start): delta += alpha p;  r -= alpha A p;  p = r + beta p -- on the owned
         // pixels and, with the same fused operations, on the ring (after the last iteration only delta survives)
         accQ = 0;
@@ -417,6 +506,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
             const bool ownRow = h >= 2 && h < R + 2;
             const T apv = ownRow ? (writer ? (AP_LDS ? apL[(AP_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] : apOwn[!AP_LDS && ownRow ? h - 2 : 0]) : ring[h]) : ring[h];
             T dNew = 0;
+            if constexpr (RESET) { if (!ownRow && !last) ringDeltaAdd(h, alpha); }      // (the split residual reset applies A to delta)
             if (ownRow) {
                 dNew = soFma(alpha, p[h], DL_LDS ? dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] : dl[!DL_LDS && ownRow ? h - 2 : 0]);
                 if (DL_LDS) dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] = dNew; else dl[!DL_LDS && ownRow ? h - 2 : 0] = dNew;
@@ -427,6 +517,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
                 p[h] = soFma(beta, p[h], r[h]);
             }
         }
+        if constexpr (RESET) qPending = !last;
         SO_MARK(5);      // update
     }
 #if SO_PROFILE

@@ -75,8 +75,8 @@ double OptAmd_PlanTrustRegionRadius(Opt_Plan* plan);
 /* Which linear-solve path the plan's last step took:
  *   0  launch-per-iteration kernels (the problem does not fit the chip, the kernel set has no on-chip solve, it is switched off: "amd_onchip" = 0 / "amd_reference_order",
  *      or a Levenberg-Marquardt solve passes a residual reset -- lIterations > residual_reset_period -- on a kernel set that keeps such a solve on chip only with
- *      "amd_onchip" = 2 (the 5-point stencils) / 3 (shape_from_shading));
- *   1  the whole linear solve of the last step ran as one persistent on-chip launch;
+ *      "amd_onchip" = 2 (the 5-point stencils) / 3 (shape_from_shading), or image_warping is given a UrShape that is not the unit pixel lattice and "amd_onchip" is below 4);
+ *   1  the whole linear solve of the last step ran as one persistent on-chip launch (also an image_warping step with a general UrShape under "amd_onchip" = 4);
  *   2  the plan is in its back-off after a failed on-chip launch: the waits of a launch's first phase are bounded by 10 ms (passing them proves the whole grid resident;
  *      a foreign tenant holding CUs makes the launch give up there, before anything has been written), the step was redone by the streaming kernels (reported on stderr the
  *      first three times) and the plan stays on them for 8 (then 16, 32 ... 1024) steps before it tries the chip again.  OptAmd_PlanDescribe carries `onchip_fallbacks` and
@@ -101,6 +101,10 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          optical_flow: 50, period 10).  It is opt-in because the two paths round differently (see OptAmd_PlanOnChipStatus).  image_warping resets on chip
  *                          under every value but 0; shape_from_shading keeps such a solve on the launch-per-iteration loop under 1 and 2.  3: as 2, and shape_from_shading
  *                          too (sfs_onchipPcg's third mode; the reference's own caller runs lIterations = 10 with the period at 10, so only longer solves get here).
+ *                          4: as 3, and image_warping takes the on-chip solve for ANY UrShape (image_warping.t:4 declares it an ordinary input array), Gauss-Newton and
+ *                          Levenberg-Marquardt, on one GPU, for images of up to 2048 pixels per CU in float (524 k pixels on 256 CUs) and 1024 in double
+ *                          (iw_onchipPcgGeneral); under 0-3 only the unit pixel lattice does and any other rest shape runs one launch per PCG iteration.  On a unit
+ *                          lattice 4 takes the same kernel as 1: the same bits.  Row slabs keep the unit-lattice rule.  Opt-in for the same reason as 2 and 3.
  * OptAmd_PlanDescribe reports the choice.  (The environment switches OPT_AMD_ONEKERNEL / OPT_AMD_ONCHIP remain as process-wide development overrides.) */
 
 /* The float4 copy rate of this box in GB/s: `bytes` moved in total per repetition (half read, half written; device memory allocated and freed inside the call),

@@ -184,6 +184,10 @@ struct EnergyOps {
     virtual bool slabOnChipAvailable(int /*lIterations*/) { return false; }
     int (*onChipPlan)(void*, int, int, int, long, OptAmd_OnChipLinks*) = nullptr;
     void* onChipCtx = nullptr;
+    // The plan's amd_onchip and the solver's Jacobi preconditioner vector, set by the solver before it binds, initialises a linear system or asks describe(): a kernel set whose
+    // on-chip solve depends on the level in Gauss-Newton too, or reads the preconditioner from memory (image_warping with a general UrShape, level 4), finds them here
+    int onChipLevel = 1;
+    T* onChipPre = nullptr;
     // Row slabs, behind a pcgSolveOnChip launch (which then applies nothing itself): onChipVerdict leaves this rank's verdict (0 fine / 1 failed) in a device scalar, the
     // solver all-reduces it, onChipApply applies X += delta iff the sum is 0 -- every rank keeps its update or none does -- and tells the host (OnchipGuard::failedNow).
     virtual void onChipVerdict(double* /*out*/, bool /*refused*/, LaunchCtx&) {}

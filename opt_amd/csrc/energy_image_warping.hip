@@ -133,18 +133,22 @@ struct ImageWarpingOps : EnergyOps<T> {
     bool fits32() const { return (unsigned long long)A.W * A.H * 3ull * sizeof(T) < (1ull << 32); }      // vectors below 4 GiB: buffer-descriptor offsets are 32-bit
     bool fastGN() const { return !this->slab.active && fits32(); }      // single GPU: the marching PCGInit1 and the single-kernel / on-chip loops
     T *initR = nullptr, *initP = nullptr; Reduction* initRed = nullptr; bool initHint = false, initPending = false, deltaZero = false;
+    // amd_onchip >= 4: the on-chip solve also for a general UrShape (single GPU; row slabs keep the unit-lattice rule)
+    bool generalOnChipWanted() const { return this->onChipLevel >= 4 && !this->slab.active && this->onChipPre != nullptr; }
     void launchJtf(bool lat, LaunchCtx& ctx, Reduction* cost = nullptr, const JtfLm<T>* lmInit = nullptr) {
         ScopedKernel k(ctx, cost ? "computeCost+PCGInit1" : "PCGInit1");
         int gx, gy, rpg; marchGrid(A.yEnd - A.yBegin, gx, gy, rpg);
+        JtfLm<T> G{};      // general UrShape, Gauss-Newton: the march also leaves M_a in the preconditioner vector for a plan that may take the on-chip solve (iw_onchipPcgGeneral)
+        if (generalOnChipWanted()) G.pre = this->onChipPre;
         if (cost) {
             if (lat) iw_jtfMarch<T, true, true><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, cost->partials, rpg, gx, gy);
-            else iw_jtfMarch<T, false, true><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, cost->partials, rpg, gx, gy);
+            else iw_jtfMarch<T, false, true><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, cost->partials, rpg, gx, gy, G);
             cost->n = gx * gy;
         } else if (lmInit) {
             if (lat) iw_jtfMarch<T, true, false, true><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, nullptr, rpg, gx, gy, *lmInit);
             else iw_jtfMarch<T, false, false, true><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, nullptr, rpg, gx, gy, *lmInit);
         } else if (lat) iw_jtfMarch<T, true, false><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, nullptr, rpg, gx, gy);
-        else iw_jtfMarch<T, false, false><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, nullptr, rpg, gx, gy);
+        else iw_jtfMarch<T, false, false><<<gx * gy, kBlock, 0, ctx.stream>>>(A, initR, initP, initRed->partials, nullptr, rpg, gx, gy, G);
         initRed->n = gx * gy;
     }
     // PCGInit1 + PCGInit1_Finish for the Gauss-Newton loops: r = -J^T F, p = M r, partial sums of r.p -- one marching kernel (no cos/sin table, no diag /
@@ -410,7 +414,7 @@ struct ImageWarpingOps : EnergyOps<T> {
     // ---- the whole linear solve on chip (iw_onchip.h): unit lattice, Gauss-Newton (also on row slabs) or Levenberg-Marquardt, tiles <= CUs ------------------------------------------
     // OPT_AMD_ONCHIP* (onchip_sync.h OnchipGuard); OPT_AMD_ONCHIP_FLAT=n: grids of up to n workgroups sum flat instead of through the two-level tree (same bits either way).
     struct OcVariant { int rows; bool apLds, deltaGlb; const void* fn; size_t lds; int occ; };
-    std::vector<OcVariant> ocVariants, ocVariantsLM;
+    std::vector<OcVariant> ocVariants, ocVariantsLM, ocVariantsGeneral, ocVariantsGeneralLM;      // (General: any UrShape, amd_onchip >= 4)
     OnchipGuard guard;
     OnchipGuard* onChipGuard() override { return &guard; }
     int ocFlatMax = 256; long long* ocProf = nullptr;
@@ -426,12 +430,19 @@ struct ImageWarpingOps : EnergyOps<T> {
             ocVariantsLM.push_back({2, false, false, (const void*)iw_onchipPcg<T, 2, false, false, true>, OcLds<T>::total(2, false, true), 0});
             ocVariantsLM.push_back({4, false, false, (const void*)iw_onchipPcg<T, 4, false, false, true>, OcLds<T>::total(4, false, true), 0});
             ocVariantsLM.push_back({8, false, false, (const void*)iw_onchipPcg<T, 8, false, false, true>, OcLds<T>::total(8, false, true), 0});
+            // general UrShape: U, M_a and CtC_a per pixel in registers; up to 2048 pixels per CU
+            ocVariantsGeneral.push_back({2, false, false, (const void*)iw_onchipPcgGeneral<T, 2, false>, OcLds<T>::totalGeneral(2, false), 0});
+            ocVariantsGeneral.push_back({4, false, false, (const void*)iw_onchipPcgGeneral<T, 4, false>, OcLds<T>::totalGeneral(4, false), 0});
+            ocVariantsGeneralLM.push_back({2, false, false, (const void*)iw_onchipPcgGeneral<T, 2, true>, OcLds<T>::totalGeneral(2, true), 0});
+            ocVariantsGeneralLM.push_back({4, false, false, (const void*)iw_onchipPcgGeneral<T, 4, true>, OcLds<T>::totalGeneral(4, true), 0});
         } else {
             ocVariants.push_back({2, false, false, (const void*)iw_onchipPcg<T, 2, false, false>, OcLds<T>::total(2, false), 0});
             ocVariants.push_back({4, false, false, (const void*)iw_onchipPcg<T, 4, false, false>, OcLds<T>::total(4, false), 0});      // (double: up to 2048 pixels per CU)
             ocVariantsLM.push_back({2, false, false, (const void*)iw_onchipPcg<T, 2, false, false, true>, OcLds<T>::total(2, false, true), 0});      // (double LM: b and the halo copies of delta do not fit the LDS at ROWS = 4)
+            ocVariantsGeneral.push_back({2, false, false, (const void*)iw_onchipPcgGeneral<T, 2, false>, OcLds<T>::totalGeneral(2, false), 0});      // (double: up to 1024 pixels per CU)
+            ocVariantsGeneralLM.push_back({2, false, false, (const void*)iw_onchipPcgGeneral<T, 2, true>, OcLds<T>::totalGeneral(2, true), 0});
         }
-        for (auto* vs : {&ocVariants, &ocVariantsLM})
+        for (auto* vs : {&ocVariants, &ocVariantsLM, &ocVariantsGeneral, &ocVariantsGeneralLM})
             for (auto& v : *vs) {
                 if (hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds) != hipSuccess) { (void)hipGetLastError(); v.occ = 0; continue; }      // (a variant the device cannot hold is simply not offered)
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v.occ, v.fn, kOcBlock, v.lds) != hipSuccess) { (void)hipGetLastError(); v.occ = 0; }
@@ -439,11 +450,11 @@ struct ImageWarpingOps : EnergyOps<T> {
             }
     }
     // Which variant, if any: the smallest ROWS whose tiles fit one per CU.  A slab's owned rows must be whole tiles (its last tile row faces the next rank's first).
-    const OcVariant* ocSelect(int& tX, int& tY, bool lmv = false) {
+    const OcVariant* ocSelect(int& tX, int& tY, bool lmv = false, bool general = false) {
         ocInit();
         tX = divUp(A.W, kOcTileW);
         const int rowsOwned = A.yEnd - A.yBegin;
-        for (const auto& v : lmv ? ocVariantsLM : ocVariants) {
+        for (const auto& v : general ? (lmv ? ocVariantsGeneralLM : ocVariantsGeneral) : (lmv ? ocVariantsLM : ocVariants)) {
             if (guard.forceRows && v.rows != guard.forceRows) continue;
             const int th = kOcWavesY * v.rows;
             if (this->slab.active && rowsOwned % th != 0) continue;
@@ -466,9 +477,11 @@ struct ImageWarpingOps : EnergyOps<T> {
         if (slabMode && (traceDev || !slabOnChipAvailable(L))) return false;
         resolveLattice();
         if (initPending && initHint && !lattice) { launchJtf(false, ctx); initHint = false; }      // PCGInit1 ran on the previous bind's verdict (see beginLoop)
-        if (!lattice) return false;
+        // a general UrShape: for a plan that opted in (amd_onchip >= 4), on one GPU; M_a (LM: and CtC_a) of every pixel is in the solver's vectors by now (iw_jtfMarch)
+        const bool general = !lattice;
+        if (general && !(generalOnChipWanted() && !slabMode && (!lmArgs || lmArgs->CtC))) return false;
         int tX = 0, tY = 0;
-        const OcVariant* V = ocSelect(tX, tY, lmArgs != nullptr);
+        const OcVariant* V = ocSelect(tX, tY, lmArgs != nullptr, general);
         if (!V) return false;
         const int G = tX * tY;
         if (lmArgs && G > ocFlatMax) return false;      // (the LM variants sum flat)
@@ -496,7 +509,8 @@ struct ImageWarpingOps : EnergyOps<T> {
         const unsigned tag0 = guard.tags(lmArgs ? 2u * (unsigned)L : (unsigned)L, ctx.stream);      // (an LM iteration that ends with the split residual reset has two phases)
         const OcTimeouts tmo = guard.timeouts(L, slabMode);
         OnchipArgs<T> K{A.W, A.H, tX, tY, G, A.yBegin, A.yEnd, links, r0, p0, A.Angle, A.flags, delta, A.w_fit, A.w_reg, L, tag0, G <= ocFlatMax ? 1 : 0, ocS, lmArgs ? lmArgs->breakInfo : traceDev,
-                        tmo.later, tmo.first, ocProf, guard.failAtThisLaunch(), T(0), T(0), T(0), T(0), 1};
+                        tmo.later, tmo.first, ocProf, guard.failAtThisLaunch(), T(0), T(0), T(0), T(0), 1,
+                        A.UrShape, this->onChipPre, lmArgs ? lmArgs->CtC : nullptr};
         K.S.bad = guard.bad; K.S.hostErr = guard.hostErr;
         if (lmArgs) { K.lmRadius = lmArgs->radius; K.lmMin = lmArgs->minLm; K.lmMax = lmArgs->maxLm; K.qTolerance = lmArgs->qTolerance; K.resetPeriod = lmArgs->resetPeriod; }
         {
@@ -545,7 +559,7 @@ struct ImageWarpingOps : EnergyOps<T> {
     std::string describe(int L, bool lmv, const OnChipLm<T>*) override {      // ("key=value; ..." -- no ';' inside a value; the LM variants do the residual reset on chip whatever the controls)
         const Slab& sl = this->slab;
         const int rowsOwned = (sl.active ? sl.yEnd - sl.yBegin : A.H);
-        char buf[900];
+        char buf[1400];
         if (sl.active) { A.yBegin = sl.yBegin; A.yEnd = sl.yEnd; } else { A.yBegin = 0; A.yEnd = A.H; }      // (what bind() will set: ocSelect reads them)
         int tX = 0, tY = 0;
         const bool eligible = guard.usable() && L > 0 && !(lmv && sl.active);
@@ -570,7 +584,22 @@ struct ImageWarpingOps : EnergyOps<T> {
             snprintf(buf, sizeof buf, "path=one launch per PCG iteration (iw_pcgIter2%s); why_not_on_chip=%s; slab_rows=%d; ghost_rows=%d; workgroup_cap=%s; per_iteration_cross_rank=%s",
                      lmv ? ", LM" : "", why.c_str(), rowsOwned, sl.active ? sl.ghost : 0, cap.c_str(), cross.c_str());
         }
-        return buf;
+        if (this->onChipLevel < 4) return buf;
+        // amd_onchip >= 4: what a UrShape that is NOT the unit lattice would take
+        std::string d = buf;
+        int gX = 0, gY = 0;
+        const OcVariant* GV = (eligible && !sl.active) ? ocSelect(gX, gY, lmv, true) : nullptr;
+        if (GV && lmv && gX * gY > ocFlatMax) GV = nullptr;
+        if (GV) {
+            if (V && ghostOk) d.replace(0, d.find(';'), "path=on-chip (unit-lattice UrShape: iw_onchipPcg, any other UrShape: iw_onchipPcgGeneral)");
+            d += "; general_urshape=on-chip (iw_onchipPcgGeneral" + std::string(lmv ? ", LM" : "") + "), " + std::to_string(GV->rows) + " rows per lane, " + std::to_string(gX) + "x" + std::to_string(gY) +
+                 " tiles, " + std::to_string(GV->lds) + " B of LDS";
+        } else {
+            const std::string why = guard.whyOff() ? guard.whyOff() : sl.active ? "row slabs take the on-chip solve on a unit lattice only" : L <= 0 ? "no PCG iterations" :
+                                    "no general-UrShape variant fits one tile per CU (at most " + std::to_string(sizeof(T) == 4 ? 2048 : 1024) + " pixels per CU" + (lmv ? ", LM: at most " + std::to_string(ocFlatMax) + " tiles" : "") + ")";
+            d += "; general_urshape=one launch per PCG iteration (iw_pcgIter2" + std::string(lmv ? ", LM" : "") + "); why_not_on_chip_general=" + why;
+        }
+        return d;
     }
     bool supportsDeferredSteps() const override { return !this->slab.active; }
     bool deltaMovable() const override { return !this->slab.active; }

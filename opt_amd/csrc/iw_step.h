@@ -421,7 +421,8 @@ __global__ __launch_bounds__(kBlock) void iw_bindMarch(IWArgs<T> A, int* __restr
     if (CHECK && __any(bad) && (threadIdx.x & (kWave - 1)) == 0) __hip_atomic_store(notLattice, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// r = -J^T F, p = guardedInvert(diag J^T J) r, partial sums of r.p (the iteration kernels rebuild M themselves: no preconditioner vector is written)
+// r = -J^T F, p = guardedInvert(diag J^T J) r, partial sums of r.p (the iteration kernels rebuild M themselves: no preconditioner vector is written -- except, for a general
+// UrShape and on request (L.pre), its Angle channel, which the on-chip solve cannot rebuild for the pixels of its halo ring)
 // COST: the same pass also sums computeCost's 1/2 r^2 (iw_costMarch's expressions, operand for operand, on the same grid: the same partial sums) -- the end of one
 // Gauss-Newton step and the PCGInit1 of the next read the same unknowns, so inside Opt_ProblemSolve the two marches are one (PcgSolver: costAndJTFInit).
 // LMINIT: the pass is Levenberg-Marquardt's PCGInit1 + PCGSaveSSq + PCGFinalizeDiagonal (solver.t:361-419, 624-664; solver.hip k_finalizeDiagonal<T, true>, expression for
@@ -496,6 +497,8 @@ __global__ __launch_bounds__(kBlock) void iw_jtfMarch(IWArgs<T> A, T* __restrict
                 ((V2<T>*)L.delta)[i] = V2<T>{0, 0}; L.delta[2 * N + i] = 0;
                 ((V2<T>*)A.cs)[i] = V2<T>{cur.c, cur.s};      // the cos / sin table the LM step's other passes read (model cost, the reset's J^T J pass): iw_cossin's values
             }
+            // Gauss-Newton, general UrShape, plan opted in to the on-chip solve for it (amd_onchip >= 4): iw_onchipPcgGeneral reads M_a from the preconditioner vector
+            if constexpr (!LATTICE && !LMINIT) { if (L.pre) L.pre[2 * N + i] = mA; }
             const T p0 = mO * r0, p1 = mO * r1, p2 = mA * r2;
             rO[i] = V2<T>{r0, r1}; ra[i] = r2;
             pO[i] = V2<T>{p0, p1}; pa[i] = p2;

@@ -920,6 +920,7 @@ struct PcgSolver : SolverBase {
         timer.reset(); trace.clear();
         if (overallOpen) { timer.pool.push_back(overallStart); overallOpen = false; }
         if (timer.enabled) { overallStart = timer.get(); HIP_CHECK(hipEventRecord(overallStart, stream)); overallOpen = true; }   // "overall": init -> cleanup (solver.t:959, 1011)
+        tellOnChipLevel();
         E->bind(params, ctx);
         boundForSolve = insideSolve;
         sp.nIter = 0; patchSweep = 0;
@@ -999,7 +1000,9 @@ struct PcgSolver : SolverBase {
         onChipFailure("the solve goes back to that step");
         sp.nIter = f;
     }
+    void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipPre = preconditioner; }      // (EnergyOps::onChipLevel)
     int stepOnce(void** params, bool& again) {
+        tellOnChipLevel();
         if (!(insideSolve && boundForSolve && E->bindInvariantDuringSolve())) E->bind(params, ctx);      // (EnergyOps::bindInvariantDuringSolve: once per Opt_ProblemSolve where nothing bind() derives can have changed)
         const bool mayDefer = !lm && !distributed && insideSolve && !traceEnabled && E->supportsDeferredSteps();
         if (!pendingSteps.empty() && (!mayDefer || sp.nIter >= sp.nIterations)) {      // (cannot happen: the last step of a solve is never deferred -- kept so that no cost is ever lost)
@@ -1259,6 +1262,7 @@ struct PcgSolver : SolverBase {
     double trustRegionRadius() const override { return (double)trust_region_radius; }
     int onChipStatus() const override { return onChipOff() ? 2 : lastStepOnChip ? 1 : 0; }
     std::string describe() override {
+        tellOnChipLevel();
         std::string d = sp.amd_reference_order ? std::string("path=reference-order (PCGStep1 [+ the previous PCGStep3] and PCGStep2 per PCG iteration, r / z / A p in memory); amd_reference_order=1")
                                                : [&] { const OnChipLm<T> la = lmControls(); return E->describe(sp.lIterations, lm, lm ? &la : nullptr); }();
         if (!sp.amd_reference_order && sp.amd_onchip != 1) d += "; amd_onchip=" + std::to_string(sp.amd_onchip);

@@ -72,12 +72,7 @@ struct OnchipArgs {
     const T* UrShape; const T* pre; const T* CtC;
 };
 
-// one scalar of the halo as tagged words: a float is one word, a double two
-template <bool SYS = false> __device__ __forceinline__ void ocSend(oc_u64* box, int idx, float v, unsigned tag) { ocStore<SYS>(box + idx, tag, __float_as_uint(v)); }
-template <bool SYS = false> __device__ __forceinline__ void ocSend(oc_u64* box, int idx, double v, unsigned tag) {
-    const oc_u64 b = (oc_u64)__double_as_longlong(v);
-    ocStore<SYS>(box + 2 * idx, tag, (unsigned)b); ocStore<SYS>(box + 2 * idx + 1, tag, (unsigned)(b >> 32));
-}
+// one scalar of the halo as tagged words (a float is one word, a double two): sent with onchip_sync.h's ocSend
 __device__ __forceinline__ void ocRecv(const oc_u64* box, int idx, unsigned tag, int* bad, long long to, float& v) { v = __uint_as_float(ocAwait(box + idx, tag, bad, to)); }
 __device__ __forceinline__ void ocRecv(const oc_u64* box, int idx, unsigned tag, int* bad, long long to, double& v) {
     const unsigned lo = ocAwait(box + 2 * idx, tag, bad, to), hi = ocAwait(box + 2 * idx + 1, tag, bad, to);
@@ -135,9 +130,6 @@ __device__ __forceinline__ double ocFromRight(double old, double v) {
 }
 
 template <class T> struct __attribute__((aligned(16))) OcH4 { T v[4]; };      // {ox, oy, a, -} of p, r or A p, or {cos, sin, on, flag byte} of one halo pixel
-
-__device__ __forceinline__ float ocFma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double ocFma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // LDS carve-up (bytes), shared by the kernel and the launcher
 constexpr int kOcSumsMax = 6;                 // capacity of the per-phase sums (Gauss-Newton 4, Levenberg-Marquardt 5)

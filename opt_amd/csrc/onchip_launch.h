@@ -1,5 +1,6 @@
 // Host side of the wave-tiled on-chip linear solves -- stencil_onchip.h (5-point stencils, a one-pixel ring) and sfs_onchip.h (shape_from_shading, a two-pixel ring): the
-// time-out guard, the two tagged buffers, which variant (if any) a plan takes, the launch, the guarded X += delta behind a Gauss-Newton solve and describe()'s text.
+// time-out guard, the two tagged buffers, which variant (if any) a plan takes, the protocol's kernel arguments (OcArgs, filled by OcGrant::args), the launch,
+// the guarded X += delta behind a Gauss-Newton solve and describe()'s text.
 // The device kernels differ; what differs for the host is data (OcFamily, the variant list).  image_warping's on-chip solve (tiles, dynamic LDS, row slabs) has a
 // host side of its own (energy_image_warping.hip).
 #pragma once
@@ -25,10 +26,33 @@ struct OcPlan {
     int mode = 0, phases = 0;      // the variant's kernel (OcVariant::kernel); grid-wide waits of the solve: one per iteration and one more per in-solve residual reset (mode 2)
     explicit operator bool() const { return V != nullptr; }
 };
-// What a family fills its kernel's argument struct from; launch() is the launch of the chosen variant.
+// The kernel arguments of the protocol (onchip_sync.h ocGridSum and what goes with it): embedded in the family's own argument struct (MoArgs), filled by OcGrant::args and nowhere else.
+// (SfsOcArgs keeps its own fields in its own order: its kernels' code depends on the layout, sfs_onchip.h.)
+template <class T>
+struct OcArgs {
+    int stripsX, tilesY, G, L;
+    unsigned tag0;                      // tag of iteration 0 (tags never repeat over the life of the buffers)
+    oc_u64* slots;                      // [2][G][2 x sums per phase]
+    oc_u64* apBox;                      // [2][W * H * C * sizeof(T) / 4]
+    int* bad; long long timeoutTicks;
+    long long firstTicks;               // bound of the FIRST iteration's wait: the co-residency check (every workgroup has posted its words once it passes), before anything is written
+    int failAt;
+    int* hostErr;                       // LM (the solver applies the update itself): pinned host word a workgroup that gave up raises on its way out; GN: nullptr (ocApplyDelta tells the host)
+    const T* CtC; T qTolerance;         // LM: the clamped diagonal, q_tolerance
+    double* lmBreak;                    // pinned {iteration + 1, zeta} of the q early-out (OnChipLm::breakInfo), or nullptr
+    int resetPeriod;                    // MODE 2: every resetPeriod-th iteration (but the last) ends with the split residual reset
+};
+// What a launch is granted; the family adds its own arguments to args() and calls launch(), the launch of the chosen variant.
 struct OcGrant : OcPlan {
     const void* fn; unsigned tag0; oc_u64 *slots, *box; int* bad; OcTimeouts tmo; int failAt;
     int* hostErr;      // LM (the solver applies the update itself): the pinned word a workgroup that gave up raises on its way out; Gauss-Newton: nullptr (ocApplyDelta tells the host)
+    template <class T> OcArgs<T> args(int L, const OnChipLm<T>* lm) const {
+        OcArgs<T> a{};
+        a.stripsX = stripsX; a.tilesY = tilesY; a.G = G; a.L = L; a.tag0 = tag0; a.slots = slots; a.apBox = box;
+        a.bad = bad; a.timeoutTicks = tmo.later; a.firstTicks = tmo.first; a.failAt = failAt; a.hostErr = hostErr;
+        if (lm) { a.CtC = lm->CtC; a.qTolerance = lm->qTolerance; a.lmBreak = lm->breakInfo; a.resetPeriod = lm->resetPeriod; }
+        return a;
+    }
     bool launch(void** kargs, hipStream_t s) const { return hipLaunchKernel(fn, dim3(G), dim3(V->waves * kWave), kargs, 0, s) == hipSuccess; }
 };
 

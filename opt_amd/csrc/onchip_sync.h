@@ -4,6 +4,10 @@
 // written through, no fence, no cache write-back) and relaxed agent-scope loads on the polling side (MI355X_MICROARCH.md "handoff-1to1" / granule "R2"; measured in
 // tools/microbench_gridsync.hip).  The tag is the iteration (phase) number, so a word says by itself whether it is the one the reader waits for; tags never repeat
 // over the life of a buffer.  Every wait is bounded by the device's 100 MHz wall clock and gives up as soon as another waiter has (the `bad` word).
+// The protocol of one phase of a wave-tiled kernel is here as functions: the grid-wide sum with its one bounded wait (ocGridSum), the q early-out (ocZetaBreak), alpha and
+// beta from the totals (ocAlpha, ocBeta).  march_onchipPcg is built from them; sfs_onchipPcg keeps its own text of the same steps (it runs at the cap of the scalar
+// registers and measurably loses with them, see sfs_onchip.h) and shares the small helpers; image_warping's kernels (two-level tree, rank hop, hand-over inside the
+// workgroup) keep their own.
 #pragma once
 #include "common.h"
 #include <utility>
@@ -140,6 +144,145 @@ __device__ __forceinline__ double ocWaveSum63(double v) {
     v = ocDppAdd<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
     v = ocDppAdd<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3
     return v;
+}
+
+// one scalar as tagged words: a float is one word, a double two (ocSend); the payload of such words once they carry the tag (ocPayload)
+template <bool SYS = false> __device__ __forceinline__ void ocSend(oc_u64* box, int idx, float v, unsigned tag) { ocStore<SYS>(box + idx, tag, __float_as_uint(v)); }
+template <bool SYS = false> __device__ __forceinline__ void ocSend(oc_u64* box, int idx, double v, unsigned tag) {
+    const oc_u64 b = (oc_u64)__double_as_longlong(v);
+    ocStore<SYS>(box + 2 * idx, tag, (unsigned)b); ocStore<SYS>(box + 2 * idx + 1, tag, (unsigned)(b >> 32));
+}
+template <class T> __device__ __forceinline__ T ocPayload(const oc_u64* w) {
+    if constexpr (sizeof(T) == 4) return __uint_as_float((unsigned)w[0]);
+    else return __longlong_as_double((long long)((w[1] << 32) | (w[0] & 0xffffffffull)));
+}
+// lane l's v, in every lane (l: wave-uniform)
+template <class T> __device__ __forceinline__ T ocReadLane(T v, int l) {
+    if constexpr (sizeof(T) == 8) return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+    else return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+__device__ __forceinline__ float ocFma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double ocFma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// ---- The protocol of one phase of a wave-tiled kernel (march_onchipPcg).  A kernel keeps what is its own: the tile geometry, the march, which ring words a lane asks
+// for, the update over the held rows.  Nothing below asks which kernel calls it: what differs is a template parameter or one of the caller's callables.
+
+// The LDS of the grid-wide sum, declared __shared__ by the kernel.  NS: sums per phase; MAXG: workgroup cap of the family.
+template <int NS, int WAVES, int MAXG>
+struct OcSumLds {
+    double red[NS * WAVES];       // [sum][wave]: the waves' partial sums
+    double TOT[NS];               // the grid's totals: the same bits in every workgroup
+    int gaveUp;                   // `bad` as thread 0 read it behind the wait: uniform over the workgroup
+    unsigned W1[MAXG * 2 * NS];   // every workgroup's words, regrouped
+};
+
+// The grid-wide sum of one phase: every workgroup posts its NS partial sums as tagged words (one per half-double) into its slot of this parity, waits ONCE for all workgroups'
+// words and for the ring words the kernel asks for (posted before their owners' sums), and adds all workgroups' words in workgroup order.  Afterwards S.TOT[0 .. NS - 1]
+// hold the totals and S.gaveUp says whether a wait timed out somewhere (the kernel leaves its loop).  Called by every thread of the workgroup.
+//   part        this lane's partial sums
+//   slotPar     the parity's [G][2 NS] slot words
+//   ticks       the bound of this wait (the first phase: the co-residency bound, OcTimeouts::first)
+//   askRing()   request this lane's ring words into the kernel's own registers (a word that is not needed: preset to {0, tag})
+//   ringHere()  do all of them carry the tag?
+template <int NS, int WAVES, int MAXG, class AskRing, class RingHere>
+__device__ __forceinline__ void ocGridSum(OcSumLds<NS, WAVES, MAXG>& S, const double (&part)[NS], unsigned tag, oc_u64* slotPar, int G, int* bad, long long ticks,
+                                          AskRing&& askRing, RingHere&& ringHere) {
+    constexpr int NW = 2 * NS, kBlk = WAVES * kWave;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = blockIdx.x;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) { const double v = ocWaveSum63(part[q]); if (lane == kWave - 1) S.red[q * WAVES + wave] = v; }
+    __syncthreads();
+    if (tid < NW) {
+        double s = 0;
+        for (int w = 0; w < WAVES; ++w) s += S.red[(tid >> 1) * WAVES + w];
+        const oc_u64 b = (oc_u64)__double_as_longlong(s);
+        ocStore(slotPar + (size_t)g * NW + tid, tag, (tid & 1) ? (unsigned)(b >> 32) : (unsigned)b);
+    }
+    // ---- ONE wait: the ring words and every workgroup's sums are requested together, re-requested until all carry this phase's tag
+    // (measured: a word-major layout that lets every wave request "its" sum directly -- no staging -- makes eight workgroups post into one 64-byte line: the wait
+    //  grows from 3.5 to 5.6 us.  Workgroup-major words, thread i requests word i, the words are regrouped through LDS.)
+    constexpr int kPer = (MAXG * NW + kBlk - 1) / kBlk;
+    oc_u64 w[kPer];
+    const int nW = G * NW;
+    bool sumsOk = false, ringOk = false;
+    // requests and checks apart: the first round asks for everything at once; a later round asks again only for what has not arrived (the ring words are
+    // posted before their owners' sums and are normally there by then: the re-requests are the words of the sums)
+    auto askSums = [&]() {
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) { const int i = tid + u * kBlk; w[u] = ocLoad(slotPar + (i < nW ? i : tid % nW)); }
+    };
+    auto check = [&]() {
+        if (!sumsOk) {
+            bool ok = true;
+#pragma unroll
+            for (int u = 0; u < kPer; ++u) { const int i = tid + u * kBlk; ok = ok && (i >= nW || (unsigned)(w[u] >> 32) == tag); }
+            sumsOk = ok;
+        }
+        if (!ringOk) ringOk = ringHere();
+        return sumsOk && ringOk;
+    };
+    askSums(); askRing();
+    if (!check()) {
+        const long long t0 = wall_clock64();
+        unsigned spins = 0;
+        for (;;) {
+            __builtin_amdgcn_s_sleep(1);
+            if (!sumsOk) askSums();
+            if (!ringOk) askRing();
+            if (check()) break;
+            if ((++spins & 31u) == 0) {
+                if (__hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                if (wall_clock64() - t0 > ticks) { __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) { const int i = tid + u * kBlk; if (i < nW) S.W1[i] = (unsigned)w[u]; }
+    __syncthreads();
+    // Every workgroup adds all workgroups' words in the same order: wave q takes sum q (more sums than waves: wave 0 takes sum WAVES as well), a lane the workgroups lane,
+    // lane + 64, lane + 128, lane + 192 in that order, then the wave's DPP tree -- the same association everywhere, so the same bits.
+#pragma unroll
+    for (int pass = 0; pass < (NS + WAVES - 1) / WAVES; ++pass) {
+        const int q = wave + pass * WAVES;
+        if (q < NS) {
+            double sacc = 0;
+#pragma unroll
+            for (int c = 0; c < MAXG / kWave; ++c) {
+                const int m = lane + c * kWave;
+                const double v = m < G ? ocJoin(S.W1[m * NW + 2 * q], S.W1[m * NW + 2 * q + 1]) : 0.0;
+                sacc += v;
+            }
+            sacc = ocWaveSum63(sacc);
+            if (lane == kWave - 1) S.TOT[q] = sacc;
+        }
+    }
+    if (tid == 0) S.gaveUp = __hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+}
+
+// The q early-out (solver.t:1093-1102): zeta = mult (Q1 - Q0) / Q1 against q_tolerance.  true: break -- thread 0 of workgroup 0 leaves {reportIter, zeta} in lmBreak
+// (OnChipLm::breakInfo) for a caller who listens; else Q0 = Q1.  Every workgroup decides from the same totals.
+template <class T> __device__ __forceinline__ bool ocZetaBreak(T Q1, T& Q0, int mult, T qTolerance, double* lmBreak, int reportIter) {
+    const T zeta = T(mult) * (Q1 - Q0) / Q1;
+    if (zeta < qTolerance) {
+        if (lmBreak && blockIdx.x == 0 && threadIdx.x == 0) { lmBreak[1] = (double)zeta; lmBreak[0] = (double)reportIter; }
+        return true;
+    }
+    Q0 = Q1;
+    return false;
+}
+
+// alpha and beta from the totals (the guards of solver.t:456-459, 544-547; beta's numerator by expansion, clamped like the direct sum it replaces).  rr: sum r^2 in front
+// of this iteration -- alphaNum itself but for the first iteration, where the caller knows its start.
+// (Two functions, so that the caller's rr is formed behind alpha as it always was: one function that returns both makes a stencil variant that sits at its register cap spill.)
+template <class T> __device__ __forceinline__ T ocAlpha(double aNumD, double aDenD) {
+    const T aNum = (T)aNumD, aDen = (T)aDenD;
+    return (aDen > T(0)) ? aNum / aDen : T(0);
+}
+template <class T> __device__ __forceinline__ T ocBeta(T alpha, double aNumD, double s2, double s3, double rr) {
+    const T aNum = (T)aNumD;
+    const double bNumD = fmax(rr - 2.0 * (double)alpha * s2 + (double)alpha * (double)alpha * s3, 0.0);
+    return (aNum > T(0)) ? (T)bNumD / aNum : T(0);
 }
 
 // PCGLinearUpdate X += delta (solver.t:552-557) behind an on-chip Gauss-Newton solve -- unless a wait timed out: then the unknowns stay untouched and the host is told

@@ -26,6 +26,10 @@
 // In float the march of MODE 2 runs its arithmetic in double on the float operands (type M below): r = b - A delta cancels, so A delta is rounded once, not per term.
 // Every wait is bounded by the device's wall clock; a time-out raises `bad`, every workgroup leaves the loop at its next sum, nothing is written to delta and the
 // host redoes the linear solve with the marching kernels.  The grid must be co-resident (one workgroup per CU): the launcher checks workgroups <= CUs.
+// The sums and their wait below are this kernel's own text, not onchip_sync.h's ocGridSum (march_onchipPcg's): the kernel runs at the cap of the scalar registers, and
+// with the shared routine, the shared q test or the shared alpha / beta the compiler spills other scalars to vector lanes (<double, 10, 2, 8>: 314 -> 445 lane moves);
+// measured, 1024^2 double then takes 0.4-0.8 % longer per solve (profiles/onchip_shared_protocol.md).  What it takes from onchip_sync.h (ocFma, ocReadLane, ocPayload)
+// leaves the assembly of all 48 kernels as it was.
 #pragma once
 #include <type_traits>
 #include "onchip_launch.h"
@@ -70,9 +74,6 @@ struct SfsOcArgs {
 
 template <class T> struct SoRowC { T g0, g1, g2; int fb; };
 template <class T> struct SoRow { T v, rk, g0, g1, g2, wr, wc, ws; int ex; };      // a staged row: p, r, dB_I / d{d0, d1, d2}, the three mask multipliers (see the march), `not excluded`
-
-__device__ __forceinline__ float soFma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double soFma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // WAVES: waves per workgroup = per CU (4: one per SIMD, 8: two).  A marching trip is ~350 instructions whatever the row holds, so an iteration costs
 // (waves per SIMD) x (R + 4) trips: the launcher picks the (R, WAVES) that minimises it among those whose workgroups fit one per CU.
@@ -122,10 +123,6 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
 
     // the P(u) coefficient of held row h, wave-uniform: lane h computes it once, a trip reads it from there into scalar registers
     const T cyLane = coefK(A, 1, 0, yBase - 2 + lane);
-    auto uniLane = [](T v, int l) -> T {
-        if constexpr (sizeof(T) == 8) return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-        else return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-    };
 
     // ---- p_0, r_0 of the held pixels (zeros outside the image); delta = 0 ------------------------------------------------------------------------------------
     T p[HR], r[HR], dl[DL_LDS ? 1 : R], apOwn[AP_LDS ? 1 : R];
@@ -176,8 +173,8 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
     };
     auto ringDeltaAdd = [&](int h, T alpha) {      // delta += alpha p of a ring row
         const int j = h < 2 ? h : h - R;
-        if (DR_LDS) drL[(DR_LDS ? j : 0) * kSoBlock + tid] = soFma(alpha, p[h], drL[(DR_LDS ? j : 0) * kSoBlock + tid]);
-        else dr[RESET && !DR_LDS ? j : 0] = soFma(alpha, p[h], dr[RESET && !DR_LDS ? j : 0]);
+        if (DR_LDS) drL[(DR_LDS ? j : 0) * kSoBlock + tid] = ocFma(alpha, p[h], drL[(DR_LDS ? j : 0) * kSoBlock + tid]);
+        else dr[RESET && !DR_LDS ? j : 0] = ocFma(alpha, p[h], dr[RESET && !DR_LDS ? j : 0]);
     };
     unsigned phase = 0;
     bool phaseB = false, qPending = false;
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
                     n.ws = (ok && (c.fb & kSfsValid)) ? wS : M(0);
                     n.ex = in ? (c.fb & kSfsEx) : 0;
                 }
-                const M cyN = uniLane(cyLane, h);
+                const M cyN = ocReadLane(cyLane, h);
                 // b(., Y) = g1 v + g0 v(x-1) + g2 v(y-1)                                      (d B_I(c) . v)
                 const M vL = dppShift<true>(n.v);
                 const M bY = n.g1 * n.v + n.g0 * vL + n.g2 * R1.v;
@@ -416,8 +413,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
             }
 #pragma unroll
             for (int h = 0; h < HR; ++h) {
-                if constexpr (WPS == 1) ring[h] = __uint_as_float((unsigned)rw[h][0]);
-                else ring[h] = __longlong_as_double((long long)((rw[h][WPS - 1] << 32) | (rw[h][0] & 0xffffffffull)));
+                ring[h] = ocPayload<T>(rw[h]);
             }
             SO_MARK(3);      // the wait: ring + sums words
 #pragma unroll
@@ -461,7 +457,7 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
                 for (int h = 0; h < HR; ++h) {
                     const bool ownRow = h >= 2 && h < R + 2;
                     if (!(ownRow && writer)) r[h] = ring[h];
-                    p[h] = soFma(betaB, p[h], r[h]);
+                    p[h] = ocFma(betaB, p[h], r[h]);
                 }
                 qPending = false; accQ = 0; phaseB = false;
                 SO_MARK(5);
@@ -489,8 +485,8 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
                 for (int h = 0; h < HR; ++h) {
                     const bool ownRow = h >= 2 && h < R + 2;
                     if (!ownRow) ringDeltaAdd(h, alpha);
-                    else if (DL_LDS) dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] = soFma(alpha, p[h], dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid]);
-                    else dl[!DL_LDS && ownRow ? h - 2 : 0] = soFma(alpha, p[h], dl[!DL_LDS && ownRow ? h - 2 : 0]);
+                    else if (DL_LDS) dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] = ocFma(alpha, p[h], dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid]);
+                    else dl[!DL_LDS && ownRow ? h - 2 : 0] = ocFma(alpha, p[h], dl[!DL_LDS && ownRow ? h - 2 : 0]);
                 }
                 aNumA = aNum; phaseB = true;
                 SO_MARK(5);
@@ -508,13 +504,13 @@ __global__ __launch_bounds__(WAVES * kWave) void sfs_onchipPcg(SfsOcArgs<T> K) {
             T dNew = 0;
             if constexpr (RESET) { if (!ownRow && !last) ringDeltaAdd(h, alpha); }      // (the split residual reset applies A to delta)
             if (ownRow) {
-                dNew = soFma(alpha, p[h], DL_LDS ? dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] : dl[!DL_LDS && ownRow ? h - 2 : 0]);
+                dNew = ocFma(alpha, p[h], DL_LDS ? dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] : dl[!DL_LDS && ownRow ? h - 2 : 0]);
                 if (DL_LDS) dlL[(DL_LDS && ownRow ? h - 2 : 0) * kSoBlock + tid] = dNew; else dl[!DL_LDS && ownRow ? h - 2 : 0] = dNew;
             }
             if (!last) {
-                r[h] = soFma(-alpha, apv, r[h]);
+                r[h] = ocFma(-alpha, apv, r[h]);
                 if (LM && ownRow && writer && yBase + (h - 2) < A.H) accQ += (double)(T(0.5) * (dNew * (r[h] + bL[(LM && ownRow ? h - 2 : 0) * kSoBlock + tid])));      // solver.t:483-485
-                p[h] = soFma(beta, p[h], r[h]);
+                p[h] = ocFma(beta, p[h], r[h]);
             }
         }
         if constexpr (RESET) qPending = !last;

@@ -2,7 +2,9 @@
 // of a Gauss-Newton step as one persistent launch whose loop state never leaves the chip.
 //
 // What it replaces: the reference's loop `for lIter = 0, lIterations do PCGStep1; PCGStep2; PCGStep3 end` (solverGPUGaussNewton.t:1056-1092) -- one marching launch per
-// iteration in march_pcgIter, 11-16 us each on images that are all launch latency (BASELINE config 1: poisson 256^2).  The protocol is sfs_onchip.h's with a one-pixel ring:
+// iteration in march_pcgIter, 11-16 us each on images that are all launch latency (BASELINE config 1: poisson 256^2).  The protocol is sfs_onchip.h's with a one-pixel ring
+// (the sums, their one wait, the q test, alpha / beta are onchip_sync.h's ocGridSum, ocZetaBreak, ocAlpha / ocBeta; this file keeps the tile, Op::apply, which ring words a
+// lane asks for and the update over the held rows):
 //   tile    a WAVE holds 64 columns x (R + 2) rows of p and r in registers and owns the 62 x R pixels in the middle; the ring is updated by the holder with the owner's
 //           alpha, beta and the same fused operations, so the search direction never travels;
 //   A p     Op::apply on the owned rows (neighbouring columns: whole-wave DPP shifts; rows above / below: the lane's own registers); flag bit and operator coefficients
@@ -33,22 +35,11 @@ constexpr int kMoNSMax = 5, kMoNWMax = 2 * kMoNSMax;   // sums per iteration (Ga
 
 template <class T>
 struct MoArgs {
+    OcArgs<T> oc;                           // the protocol's arguments (onchip_launch.h OcGrant::args): the grid, the tags, the tagged buffers, the bounds of the waits, the LM controls
     int W, H;
     const T* r0; const T* p0; T* delta;     // solver vectors: C channels per pixel, interleaved
     const uint8_t* flags; const T* coef;    // Op::kMasked / Op::kCoef
-    int stripsX, tilesY, G, L;
-    unsigned tag0;                          // tag of iteration 0 (tags never repeat over the life of the buffers)
-    oc_u64* slots;                          // [2][G][8]
-    oc_u64* apBox;                          // [2][W * H * C * sizeof(T) / 4]
-    int* bad; long long timeoutTicks; int failAt;
-    long long firstTicks;      // bound of the FIRST iteration's wait: the co-residency check (every workgroup has posted its words once it passes), before anything is written
-    const T* CtC; T qTolerance; int* hostErr;      // LM: the clamped diagonal, q_tolerance, the pinned word a workgroup that gave up raises (the solver applies the update itself)
-    double* lmBreak;                               // pinned {iteration + 1, zeta} of the q early-out (OnChipLm::breakInfo), or nullptr
-    int resetPeriod;                               // MODE 2: every resetPeriod-th iteration (but the last) ends with the split residual reset
 };
-
-__device__ __forceinline__ float moFma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double moFma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // MODE: 0 Gauss-Newton, 1 Levenberg-Marquardt, 2 Levenberg-Marquardt with the split residual reset inside the solve
 template <class T, class Op, int R, int WAVES, int MODE>
@@ -58,9 +49,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
     constexpr int C = Op::C, HR = R + 2, kBlk = WAVES * kWave, WPS = (int)sizeof(T) / 4;
     constexpr int kCoefN = Op::kCoef > 0 ? Op::kCoef : 1;
     using Vec = MVec<T, C>; using Coef = MVec<T, kCoefN>;
-    __shared__ double red[kMoNS * WAVES];
-    __shared__ double TOT[kMoNS + 1];
-    __shared__ unsigned W1[kMoMaxG * kMoNW];
+    __shared__ OcSumLds<kMoNS, WAVES, kMoMaxG> sums;
     constexpr bool AP_LDS = C * sizeof(T) * R >= 128;      // where the registers are short, A p of the owned pixels waits in LDS between the stencil and the update: [row][channel][thread]
     __shared__ T apL[AP_LDS ? R * C * kBlk : 1];
     constexpr bool DL_LDS = AP_LDS && Op::kCoef >= 4 && (C + Op::kCoef) * sizeof(T) * R >= 256;      // ... and, for the fattest pixels (four channels + four coefficients), delta itself
@@ -68,8 +57,8 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
     __shared__ T bL[LM ? R * C * kBlk : 1];      // LM: b = r_0 of the owned pixels (for Q)
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = blockIdx.x;
     const int tile = g * WAVES + wave;
-    const int sx = tile % K.stripsX, ty = tile / K.stripsX;
-    const bool idle = ty >= K.tilesY;                  // (wave-uniform) a wave without a tile: contributes zeros to the sums
+    const int sx = tile % K.oc.stripsX, ty = tile / K.oc.stripsX;
+    const bool idle = ty >= K.oc.tilesY;                  // (wave-uniform) a wave without a tile: contributes zeros to the sums
     const int x = sx * kMoSpan + lane - 1;
     const int yBase = ty * R;                          // first owned row; held row h is image row yBase - 1 + h
     const bool xin = !idle && x >= 0 && x < K.W;
@@ -77,8 +66,8 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
     const bool hasL = x >= 1, hasR = x + 1 < K.W;
     const int xc = min(max(x, 0), K.W - 1);
     const int N = K.W * K.H;
-    int* const bad = K.bad;
-    const long long to = K.timeoutTicks;
+    int* const bad = K.oc.bad;
+    const long long to = K.oc.timeoutTicks;
     // scalar (pixel i, channel c) of a solver vector: C interleaved channels, or -- Op::kSplit31 -- a 3-channel image followed by a 1-channel image (energy.h)
     auto at = [&](long i, int c) -> long { if constexpr (Op::kSplit31) return c < 3 ? i * 3 + c : 3L * N + i; else return i * C + c; };
 
@@ -101,7 +90,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
         onBits |= on ? (1u << h) : 0u;
         if (LM && h >= 1 && h <= R) {
 #pragma unroll
-            for (int c = 0; c < C; ++c) { const T cv = K.CtC[at(i, c)]; ctc[LM ? h - 1 : 0].v[c] = on ? cv : T(0); bL[((LM ? h - 1 : 0) * C + c) * kBlk + tid] = r[h].v[c]; }      // b = r_0 (solver.t:657)
+            for (int c = 0; c < C; ++c) { const T cv = K.oc.CtC[at(i, c)]; ctc[LM ? h - 1 : 0].v[c] = on ? cv : T(0); bL[((LM ? h - 1 : 0) * C + c) * kBlk + tid] = r[h].v[c]; }      // b = r_0 (solver.t:657)
         }
     }
 #pragma unroll
@@ -129,14 +118,14 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
     bool phaseB = false, qPending = false;
     T aNumA = 0;
 
-    for (int k = 0; k < K.L; k += phaseB ? 0 : 1) {
-        const unsigned tag = K.tag0 + (RESET ? phase : (unsigned)k);
+    for (int k = 0; k < K.oc.L; k += phaseB ? 0 : 1) {
+        const unsigned tag = K.oc.tag0 + (RESET ? phase : (unsigned)k);
         const int par = (int)(tag & 1u);
-        oc_u64* const box = K.apBox + (size_t)par * boxStride;
-        oc_u64* const slotPar = K.slots + (size_t)par * K.G * kMoNW;
-        if (k == K.failAt && g == 0 && tid == 0) __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        oc_u64* const box = K.oc.apBox + (size_t)par * boxStride;
+        oc_u64* const slotPar = K.oc.slots + (size_t)par * K.oc.G * kMoNW;
+        if (k == K.oc.failAt && g == 0 && tid == 0) __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const bool first = k == 0;
-        const bool resetIt = RESET && k + 1 < K.L && (k + 1) % K.resetPeriod == 0;      // this iteration ends with the split residual reset: r is formed anew, nobody needs the ring's A p
+        const bool resetIt = RESET && k + 1 < K.oc.L && (k + 1) % K.oc.resetPeriod == 0;      // this iteration ends with the split residual reset: r is formed anew, nobody needs the ring's A p
 
         // ---- PCGStep1: A p_k on the owned pixels, with the four sums (march_pcgIter's expressions) --------------------------------------------------------------
         double accDen = 0, accNum = 0, acc2 = 0, acc3 = 0, accX = 0;      // accX (LM): sum r_0^2 in iteration 0, the Q of the iteration before in the others
@@ -170,12 +159,9 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
                             accX += (double)(T(0.5) * (dc.v[c] * (rn + bv)));      // solver.t:483-485
                         }
                         if (h == 1 || h == R || lane == 1 || lane == kMoSpan) {
-                            const size_t i = (size_t)(pixBase + h * K.W) * C * WPS;
+                            const int i = (pixBase + h * K.W) * C;      // (int index: the launcher grants images below 2^30 bytes, OnchipLauncher::plan)
 #pragma unroll
-                            for (int c = 0; c < C; ++c) {
-                                if constexpr (WPS == 1) ocStore(box + i + c, tag, __float_as_uint((float)r[h].v[c]));
-                                else { const oc_u64 b = (oc_u64)__double_as_longlong((double)r[h].v[c]); ocStore(box + i + 2 * c, tag, (unsigned)b); ocStore(box + i + 2 * c + 1, tag, (unsigned)(b >> 32)); }
-                            }
+                            for (int c = 0; c < C; ++c) ocSend(box, i + c, r[h].v[c], tag);
                         }
                     }
                     du = dc; dc = dd;
@@ -202,54 +188,31 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
                     }
                     // the tile's outermost rows / columns: to the tagged image, for whoever holds them as ring
                     if (!resetIt && (h == 1 || h == R || lane == 1 || lane == kMoSpan)) {
-                        const size_t i = (size_t)(pixBase + h * K.W) * C * WPS;
+                        const int i = (pixBase + h * K.W) * C;      // (int, as above)
 #pragma unroll
-                        for (int c = 0; c < C; ++c) {
-                            if constexpr (WPS == 1) ocStore(box + i + c, tag, __float_as_uint((float)o.v[c]));
-                            else { const oc_u64 b = (oc_u64)__double_as_longlong((double)o.v[c]); ocStore(box + i + 2 * c, tag, (unsigned)b); ocStore(box + i + 2 * c + 1, tag, (unsigned)(b >> 32)); }
-                        }
+                        for (int c = 0; c < C; ++c) ocSend(box, i + c, o.v[c], tag);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
 
-        // ---- the grid-wide sums; the ring's A p (phase B: the ring's new r) is collected inside the wait ----------------------------------------------------
+        // ---- the grid-wide sums (onchip_sync.h ocGridSum); the ring's A p (phase B: the ring's new r) is collected inside its ONE wait ---------------------------
+        // Ring requests: every lane asks for its column's pixel of the rows above and below the tile; the two side columns are asked for by ONE lane per pixel
+        // (lane h: the left neighbour of row h, lane 32 + h: the right one) and handed to lanes 0 / 63 through scalar registers afterwards -- a lane holds three
+        // pixels' words during the wait instead of R + 2 (the difference is what lets 16 rows per wave fit).
+        static_assert(R + 1 < 32, "one lane per side pixel");
+        oc_u64 rw[3][C * WPS];      // top, bottom, side
         {
             if (LM && !first && !(RESET && phaseB)) accX = accQ;
-            double v4[kMoNS];
-            v4[0] = accNum; v4[1] = accDen; v4[2] = acc2; v4[3] = acc3;
-            if constexpr (LM) v4[4] = accX;
-#pragma unroll
-            for (int q = 0; q < kMoNS; ++q) { v4[q] = ocWaveSum63(v4[q]); if (lane == kWave - 1) red[q * WAVES + wave] = v4[q]; }
-        }
-        __syncthreads();
-        if (tid < kMoNW) {
-            double s = 0;
-            for (int w = 0; w < WAVES; ++w) s += red[(tid >> 1) * WAVES + w];
-            const oc_u64 b = (oc_u64)__double_as_longlong(s);
-            ocStore(slotPar + (size_t)g * kMoNW + tid, tag, (tid & 1) ? (unsigned)(b >> 32) : (unsigned)b);
-        }
-        Vec ring[HR];
-        {
-            constexpr int kPer = (kMoMaxG * kMoNW + kBlk - 1) / kBlk;
-            oc_u64 w[kPer];
-            const int nW = K.G * kMoNW;
-            const bool lastIt = k + 1 == K.L || (RESET && resetIt && !phaseB);      // (after the last iteration only delta survives: nobody needs the ring; nor in front of a reset)
-            // Ring requests: every lane asks for its column's pixel of the rows above and below the tile; the two side columns are asked for by ONE lane per pixel
-            // (lane h: the left neighbour of row h, lane 32 + h: the right one) and handed to lanes 0 / 63 through scalar registers afterwards -- a lane holds three
-            // pixels' words during the wait instead of R + 2 (the difference is what lets 16 rows per wave fit).
-            static_assert(R + 1 < 32, "one lane per side pixel");
+            double part[kMoNS];
+            part[0] = accNum; part[1] = accDen; part[2] = acc2; part[3] = acc3;
+            if constexpr (LM) part[4] = accX;
+            const bool lastIt = k + 1 == K.oc.L || (RESET && resetIt && !phaseB);      // (after the last iteration only delta survives: nobody needs the ring; nor in front of a reset)
             const int sRow = lane & 31, sX = (lane < 32) ? sx * kMoSpan - 1 : sx * kMoSpan + kMoSpan, sY = yBase - 1 + sRow;
             const bool needTop = !lastIt && rowIn(0), needBot = !lastIt && rowIn(HR - 1);
             const bool needSide = !lastIt && !idle && sRow >= 1 && sRow <= R && sX >= 0 && sX < K.W && sY < K.H;
             const size_t iTop = (size_t)pixBase * C * WPS, iBot = (size_t)(pixBase + (HR - 1) * K.W) * C * WPS, iSide = needSide ? ((size_t)sY * K.W + sX) * C * WPS : 0;
-            oc_u64 rw[3][C * WPS];      // top, bottom, side
-            bool sumsOk = false, ringOk = false;
-            auto askSums = [&]() {
-#pragma unroll
-                for (int u = 0; u < kPer; ++u) { const int i = tid + u * kBlk; w[u] = ocLoad(slotPar + (i < nW ? i : tid % nW)); }
-            };
             auto askRing = [&]() {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
@@ -263,87 +226,30 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
                     }
                 }
             };
-            auto check = [&]() {
-                if (!sumsOk) {
-                    bool ok = true;
+            auto ringHere = [&]() {
+                bool ok = true;
 #pragma unroll
-                    for (int u = 0; u < kPer; ++u) { const int i = tid + u * kBlk; ok = ok && (i >= nW || (unsigned)(w[u] >> 32) == tag); }
-                    sumsOk = ok;
-                }
-                if (!ringOk) {
-                    bool ok = true;
+                for (int j = 0; j < 3; ++j)
 #pragma unroll
-                    for (int j = 0; j < 3; ++j)
-#pragma unroll
-                        for (int q = 0; q < C * WPS; ++q) ok = ok && (unsigned)(rw[j][q] >> 32) == tag;
-                    ringOk = ok;
-                }
-                return sumsOk && ringOk;
+                    for (int q = 0; q < C * WPS; ++q) ok = ok && (unsigned)(rw[j][q] >> 32) == tag;
+                return ok;
             };
-            askSums(); askRing();
-            if (!check()) {
-                const long long t0 = wall_clock64();
-                unsigned spins = 0;
-                for (;;) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (!sumsOk) askSums();
-                    if (!ringOk) askRing();
-                    if (check()) break;
-                    if ((++spins & 31u) == 0) {
-                        if (__hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-                        if (wall_clock64() - t0 > (k == 0 && !(RESET && phaseB) ? K.firstTicks : to)) { __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-                    }
-                }
-            }
-            auto decode = [&](const oc_u64 (&q)[C * WPS], int c) -> T {
-                if constexpr (WPS == 1) return __uint_as_float((unsigned)q[c]);
-                else return __longlong_as_double((long long)((q[2 * c + 1] << 32) | (q[2 * c] & 0xffffffffull)));
-            };
-            auto laneOf = [](T v, int l) -> T {
-                if constexpr (sizeof(T) == 8) return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-                else return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-            };
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                ring[0].v[c] = decode(rw[0], c); ring[HR - 1].v[c] = decode(rw[1], c);
-                const T sv = decode(rw[2], c);
-#pragma unroll
-                for (int h = 1; h <= R; ++h) { const T lft = laneOf(sv, h), rgt = laneOf(sv, 32 + h); ring[h].v[c] = lane == 0 ? lft : rgt; }      // (only lanes 0 and 63 use them)
-            }
-#pragma unroll
-            for (int u = 0; u < kPer; ++u) { const int i = tid + u * kBlk; if (i < nW) W1[i] = (unsigned)w[u]; }
-            __syncthreads();
-            // every workgroup adds all workgroups' words in the same order: wave q takes sum q, a lane the workgroups lane, lane + 64, lane + 128, lane + 192 in that
-            // order, then the wave's DPP tree -- the same association everywhere, so the same bits
-#pragma unroll
-            for (int pass = 0; pass < (kMoNS + WAVES - 1) / WAVES; ++pass) {      // (five sums on four waves: wave 0 takes the fifth as well)
-                const int q = wave + pass * WAVES;
-                if (q < kMoNS) {
-                    double sacc = 0;
-#pragma unroll
-                    for (int c = 0; c < kMoMaxG / kWave; ++c) {
-                        const int m = lane + c * kWave;
-                        const double v = m < K.G ? ocJoin(W1[m * kMoNW + 2 * q], W1[m * kMoNW + 2 * q + 1]) : 0.0;
-                        sacc += v;
-                    }
-                    sacc = ocWaveSum63(sacc);
-                    if (lane == kWave - 1) TOT[q] = sacc;
-                }
-            }
-            if (tid == 0) reinterpret_cast<int*>(TOT + kMoNS)[0] = __hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
+            ocGridSum(sums, part, tag, slotPar, K.oc.G, bad, k == 0 && !(RESET && phaseB) ? K.oc.firstTicks : to, askRing, ringHere);
         }
-        const double aNumD = TOT[0], aDenD = TOT[1], s2 = TOT[2], s3 = TOT[3];
-        if (reinterpret_cast<const int*>(TOT + kMoNS)[0]) { failed = true; break; }      // uniform over the workgroup: a wait timed out somewhere
+        Vec ring[HR];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            ring[0].v[c] = ocPayload<T>(rw[0] + c * WPS); ring[HR - 1].v[c] = ocPayload<T>(rw[1] + c * WPS);
+            const T sv = ocPayload<T>(rw[2] + c * WPS);
+#pragma unroll
+            for (int h = 1; h <= R; ++h) { const T lft = ocReadLane(sv, h), rgt = ocReadLane(sv, 32 + h); ring[h].v[c] = lane == 0 ? lft : rgt; }      // (only lanes 0 and 63 use them)
+        }
+        const double aNumD = sums.TOT[0], aDenD = sums.TOT[1], s2 = sums.TOT[2], s3 = sums.TOT[3];
+        if (sums.gaveUp) { failed = true; break; }      // uniform over the workgroup: a wait timed out somewhere
         if constexpr (RESET) {
             ++phase;
             if (phaseB) {
-                {      // the q test of THIS iteration: the split step delivers Q directly
-                    const T Q1 = (T)TOT[kMoNS - 1];
-                    const T zeta = T(k + 1) * (Q1 - Q0) / Q1;
-                    if (zeta < K.qTolerance) { if (K.lmBreak && blockIdx.x == 0 && tid == 0) { K.lmBreak[1] = (double)zeta; K.lmBreak[0] = (double)(k + 2); } break; }
-                    Q0 = Q1;
-                }
+                if (ocZetaBreak((T)sums.TOT[kMoNS - 1], Q0, k + 1, K.oc.qTolerance, K.oc.lmBreak, k + 2)) break;      // the q test of THIS iteration: the split step delivers Q directly
                 const T betaB = (aNumA > T(0)) ? (T)aNumD / aNumA : T(0);      // PCGStep3's guard (:544-547)
                 // r as received on the ring, then p = r + beta p everywhere: the bits of the pixel's owner
 #pragma unroll
@@ -352,7 +258,7 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
                         if (!(ownRow && writer)) r[h].v[c] = ring[h].v[c];
-                        p[h].v[c] = moFma(betaB, p[h].v[c], r[h].v[c]);
+                        p[h].v[c] = ocFma(betaB, p[h].v[c], r[h].v[c]);
                     }
                 }
                 qPending = false; accQ = 0; phaseB = false;
@@ -360,21 +266,12 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
             }
         }
         if constexpr (LM) {      // the q early-out of iteration k - 1 (solver.t:1093-1102): nothing of iteration k has been applied yet
-            if (RESET ? qPending : !first) {
-                const T Q1 = (T)TOT[4];
-                const T zeta = T(k) * (Q1 - Q0) / Q1;
-                if (zeta < K.qTolerance) { if (K.lmBreak && blockIdx.x == 0 && tid == 0) { K.lmBreak[1] = (double)zeta; K.lmBreak[0] = (double)(k + 1); } break; }
-                Q0 = Q1;
-            }
+            if ((RESET ? qPending : !first) && ocZetaBreak((T)sums.TOT[kMoNS - 1], Q0, k, K.oc.qTolerance, K.oc.lmBreak, k + 1)) break;
         }
-        // the scalars of march_pcgIter's prologue (solver.t:456-459, 544-547 guards; beta numerator by expansion, clamped like the direct sum it replaces; the start-up
-        // quirk: sum r_0^2 = 4 alphaNumerator_0, exact)
-        const T aNum = (T)aNumD, aDen = (T)aDenD;
-        const T alpha = (aDen > T(0)) ? aNum / aDen : T(0);
-        const double rr = first ? (LM ? TOT[LM ? 4 : 0] : 4.0 * aNumD) : aNumD;      // (LM starts from the preconditioned r_0: sum r_0^2 is summed directly)
-        const double bNumD = fmax(rr - 2.0 * (double)alpha * s2 + (double)alpha * (double)alpha * s3, 0.0);
-        const T beta = (aNum > T(0)) ? (T)bNumD / aNum : T(0);
-        const bool last = k + 1 == K.L;
+        // the scalars of march_pcgIter's prologue; the start-up quirk: sum r_0^2 = 4 alphaNumerator_0, exact (LM starts from the preconditioned r_0: sum r_0^2 is summed directly)
+        const T alpha = ocAlpha<T>(aNumD, aDenD);
+        const T beta = ocBeta<T>(alpha, aNumD, s2, s3, first ? (LM ? sums.TOT[kMoNS - 1] : 4.0 * aNumD) : aNumD);
+        const bool last = k + 1 == K.oc.L;
 
         if constexpr (RESET) {
             if (resetIt) {
@@ -384,12 +281,12 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
                     const bool ownRow = h >= 1 && h <= R;
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
-                        if (!ownRow) dr[h == 0 ? 0 : 1].v[c] = moFma(alpha, p[h].v[c], dr[h == 0 ? 0 : 1].v[c]);
-                        else if (DL_LDS) dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] = moFma(alpha, p[h].v[c], dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid]);
-                        else dl[!DL_LDS && ownRow ? h - 1 : 0].v[c] = moFma(alpha, p[h].v[c], dl[!DL_LDS && ownRow ? h - 1 : 0].v[c]);
+                        if (!ownRow) dr[h == 0 ? 0 : 1].v[c] = ocFma(alpha, p[h].v[c], dr[h == 0 ? 0 : 1].v[c]);
+                        else if (DL_LDS) dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] = ocFma(alpha, p[h].v[c], dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid]);
+                        else dl[!DL_LDS && ownRow ? h - 1 : 0].v[c] = ocFma(alpha, p[h].v[c], dl[!DL_LDS && ownRow ? h - 1 : 0].v[c]);
                     }
                 }
-                aNumA = aNum; phaseB = true;
+                aNumA = (T)aNumD; phaseB = true;
                 continue;
             }
         }
@@ -403,21 +300,21 @@ __global__ __launch_bounds__(WAVES * kWave) void march_onchipPcg(Op op, MoArgs<T
             for (int c = 0; c < C; ++c) {
                 const T apv = ownRow ? (writer ? (AP_LDS ? apL[((AP_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] : ap[!AP_LDS && ownRow ? h - 1 : 0].v[c]) : ring[h].v[c]) : ring[h].v[c];
                 T dNew = 0;
-                if (RESET && !ownRow && !last) dr[RESET && h != 0 ? 1 : 0].v[c] = moFma(alpha, p[h].v[c], dr[RESET && h != 0 ? 1 : 0].v[c]);      // (the split residual reset applies A to delta)
+                if (RESET && !ownRow && !last) dr[RESET && h != 0 ? 1 : 0].v[c] = ocFma(alpha, p[h].v[c], dr[RESET && h != 0 ? 1 : 0].v[c]);      // (the split residual reset applies A to delta)
                 if (ownRow) {
-                    dNew = moFma(alpha, p[h].v[c], DL_LDS ? dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] : dl[!DL_LDS && ownRow ? h - 1 : 0].v[c]);
+                    dNew = ocFma(alpha, p[h].v[c], DL_LDS ? dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] : dl[!DL_LDS && ownRow ? h - 1 : 0].v[c]);
                     if (DL_LDS) dlL[((DL_LDS && ownRow ? h - 1 : 0) * C + c) * kBlk + tid] = dNew; else dl[!DL_LDS && ownRow ? h - 1 : 0].v[c] = dNew;
                 }
                 if (!last) {
-                    r[h].v[c] = moFma(-alpha, apv, r[h].v[c]);
+                    r[h].v[c] = ocFma(-alpha, apv, r[h].v[c]);
                     if (LM && ownRow && writer && yBase - 1 + h < K.H) accQ += (double)(T(0.5) * (dNew * (r[h].v[c] + bL[((LM && ownRow ? h - 1 : 0) * C + c) * kBlk + tid])));      // solver.t:483-485
-                    p[h].v[c] = moFma(beta, p[h].v[c], r[h].v[c]);
+                    p[h].v[c] = ocFma(beta, p[h].v[c], r[h].v[c]);
                 }
             }
         }
         if constexpr (RESET) qPending = !last;
     }
-    if (failed && tid == 0 && K.hostErr) __hip_atomic_store(K.hostErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (failed && tid == 0 && K.oc.hostErr) __hip_atomic_store(K.oc.hostErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (!failed && writer) {
 #pragma unroll
         for (int i = 0; i < R; ++i) {
@@ -502,8 +399,7 @@ struct MarchOps : Base {
         if (!useMarch || traceDev || this->slab.active || !oc.plan(L, lm != nullptr, lm)) return false;      // (asked before the coefficient pass is spent)
         produceCoefficients(ctx);
         return oc.solve(L, lm, delta, *this, ctx, [&](const OcGrant& g) {
-            MoArgs<T> K{mW, mH, r0, p0, delta, marchFlags, coef, g.stripsX, g.tilesY, g.G, L, g.tag0, g.slots, g.box, g.bad, g.tmo.later, g.failAt, g.tmo.first, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0),
-                        g.hostErr, lm ? lm->breakInfo : nullptr, lm ? lm->resetPeriod : 0};
+            MoArgs<T> K{g.args(L, lm), mW, mH, r0, p0, delta, marchFlags, coef};
             Op op = marchOp();
             void* kargs[] = {(void*)&op, (void*)&K};
             return g.launch(kargs, ctx.stream);

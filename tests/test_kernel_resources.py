@@ -5,6 +5,8 @@ runtime can OFFER runs without scratch -- the persistent ("on-chip") kernels are
 kernels are sized against the register file.  Variants that would spill are not instantiated at all (Op::spills / Op::kMaxBlock); two image_warping on-chip variants
 are listed with the bytes they still hold and why, so that a regression (or an improvement) shows up here instead of in a profile.
 """
+import json
+import os
 import re
 
 import pytest
@@ -77,3 +79,18 @@ def test_the_benchmarked_kernel_has_headroom(resources):
     assert hits
     for n, r in hits.items():
         assert r["scratch"] == 0 and r["vgprs"] <= 168 and r["occupancy"] >= 3, (n, r)
+
+
+def test_wave_tiled_onchip_kernels_are_the_frozen_set(resources):
+    """Every sfs_onchipPcg<...> and march_onchipPcg<...> kernel: the set of kernels is the frozen one (no variant appeared or vanished), none uses scratch and none holds
+    more LDS than the frozen table says (tests/golden/onchip_kernel_lds.json: taken from the build in front of the commit that moved the kernels' grid-wide sum and wait
+    into onchip_sync.h; a run-time gate un-offers a stencil variant that spills without a word, so this is where it shows)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "onchip_kernel_lds.json")) as f:
+        frozen = json.load(f)["lds_bytes"]
+    now = {n: r for n, r in resources.items() if re.match(r"^(sfs_onchipPcg|march_onchipPcg)<", n)}
+    assert set(now) == set(frozen), (sorted(set(now) - set(frozen)), sorted(set(frozen) - set(now)))
+    assert len(frozen) > 100, len(frozen)
+    scratch = {n: r["scratch"] for n, r in now.items() if r["scratch"] != 0}
+    assert not scratch, scratch
+    grew = {n: (frozen[n], r["lds"]) for n, r in now.items() if r["lds"] > frozen[n]}
+    assert not grew, grew

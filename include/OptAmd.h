@@ -75,8 +75,10 @@ double OptAmd_PlanTrustRegionRadius(Opt_Plan* plan);
 /* Which linear-solve path the plan's last step took:
  *   0  launch-per-iteration kernels (the problem does not fit the chip, the kernel set has no on-chip solve, it is switched off: "amd_onchip" = 0 / "amd_reference_order",
  *      or a Levenberg-Marquardt solve passes a residual reset -- lIterations > residual_reset_period -- on a kernel set that keeps such a solve on chip only with
- *      "amd_onchip" = 2 (the 5-point stencils) / 3 (shape_from_shading), or image_warping is given a UrShape that is not the unit pixel lattice and "amd_onchip" is below 4);
- *   1  the whole linear solve of the last step ran as one persistent on-chip launch (also an image_warping step with a general UrShape under "amd_onchip" = 4);
+ *      "amd_onchip" = 2 (the 5-point stencils) / 3 (shape_from_shading), or image_warping is given a UrShape that is not the unit pixel lattice and "amd_onchip" is below 4,
+ *      or a mesh energy runs below "amd_onchip" = 5 or on a graph its one-workgroup solve does not take);
+ *   1  the whole linear solve of the last step ran as one persistent on-chip launch (also an image_warping step with a general UrShape under "amd_onchip" = 4, and an
+ *      arap_mesh_deformation / volumetric_mesh_deformation step on a small symmetric graph under "amd_onchip" = 5: one workgroup);
  *   2  the plan is in its back-off after a failed on-chip launch: the waits of a launch's first phase are bounded by 10 ms (passing them proves the whole grid resident;
  *      a foreign tenant holding CUs makes the launch give up there, before anything has been written), the step was redone by the streaming kernels (reported on stderr the
  *      first three times) and the plan stays on them for 8 (then 16, 32 ... 1024) steps before it tries the chip again.  OptAmd_PlanDescribe carries `onchip_fallbacks` and
@@ -105,6 +107,12 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          Levenberg-Marquardt, on one GPU, for images of up to 2048 pixels per CU in float (524 k pixels on 256 CUs) and 1024 in double
  *                          (iw_onchipPcgGeneral); under 0-3 only the unit pixel lattice does and any other rest shape runs one launch per PCG iteration.  On a unit
  *                          lattice 4 takes the same kernel as 1: the same bits.  Row slabs keep the unit-lattice rule.  Opt-in for the same reason as 2 and 3.
+ *                          5: as 4, and arap_mesh_deformation (and volumetric_mesh_deformation, which runs on ARAP's kernels) runs the whole linear solve, Gauss-Newton
+ *                          and Levenberg-Marquardt, as one launch of ONE workgroup (arap_onchipPcg) when the graph is symmetric, no vertex has more than 16 neighbours
+ *                          and the vertex count is within the offered variants: 1024 vertices in float and in double Gauss-Newton, 512 in double Levenberg-Marquardt
+ *                          (the reference's own meshes: small_armadillo 130 / 386 vertices, head 689).  Any other graph keeps the two launches per PCG iteration, and
+ *                          OptAmd_PlanDescribe says why (why_not_on_chip).  The kernel has no grid-wide wait and therefore no time-out path.  Under 0-4 and by default
+ *                          the mesh energies keep their bits.  Opt-in for the same reason as 2-4.
  * OptAmd_PlanDescribe reports the choice.  (The environment switches OPT_AMD_ONEKERNEL / OPT_AMD_ONCHIP remain as process-wide development overrides.) */
 
 /* The float4 copy rate of this box in GB/s: `bytes` moved in total per repetition (half read, half written; device memory allocated and freed inside the call),

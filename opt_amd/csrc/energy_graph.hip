@@ -21,6 +21,7 @@
 #include "energy.h"
 #include "graph_common.h"
 #include <hipcub/hipcub.hpp>
+#include <cstring>
 
 namespace optamd {
 namespace {
@@ -730,6 +731,12 @@ __global__ __launch_bounds__(kBlock) void arap_vertexGatherJTF(ArapArgs<T> A, Gr
     }
 }
 
+}  // namespace
+}  // namespace optamd
+#include "arap_onchip.h"      // the whole linear solve of a small symmetric graph in one workgroup (amd_onchip = 5)
+namespace optamd {
+namespace {
+
 template <class T>
 struct ArapOps : EnergyOps<T> {
     ArapArgs<T> A{};
@@ -743,6 +750,7 @@ struct ArapOps : EnergyOps<T> {
     T* D9 = nullptr; long d9Capacity = 0; int* nbr = nullptr;
     // symmetric-graph path (arap_applyEll): 16-byte planes D0, D1 (dynamic), T0, T1, U0 (per Gauss-Newton step) and the out-lists in ELL order; OPT_AMD_ARAP_SYM=0 keeps arap_applyFused
     bool useSym = true, symGraph = false;
+    int ellOverflow = 0;      // the longest out-list of a symmetric graph that left the plane path for it (> kEllMax), else 0
     ArapPlanes<T> planes{}; void* planeMem = nullptr; int* ellMem = nullptr; int* dNotSym = nullptr;
     bool symPath() const { return useGather && useSym && symGraph; }
     ~ArapOps() override {
@@ -782,7 +790,7 @@ struct ArapOps : EnergyOps<T> {
         HIP_CHECK(hipMalloc((void**)&nbr, (size_t)2 * std::max(1, A.nE) * 4));
         csr_neighbours<<<ge, kBlock, 0, st>>>(A.v0, A.v1, A.nE, outIdx, inIdx, nbr, nbr + std::max(1, A.nE));
         // does every edge come with its reverse (per vertex: out-neighbours == in-neighbours as multisets)?  Then J^T J p walks the out-lists only (arap_applySym)
-        symGraph = false;
+        symGraph = false; ellOverflow = 0;
         if (useSym) {
             if (!dNotSym) HIP_CHECK(hipMalloc((void**)&dNotSym, 4));
             HIP_CHECK(hipMemsetAsync(dNotSym, 0, 4, st));
@@ -797,7 +805,7 @@ struct ArapOps : EnergyOps<T> {
                 csr_maxDegree<<<vgrid(), kBlock, 0, st>>>(A.N, outOff, dNotSym);
                 int K = 0;
                 HIP_CHECK(hipMemcpyAsync(&K, dNotSym, 4, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st));
-                if (K > kEllMax) symGraph = false;
+                if (K > kEllMax) { symGraph = false; ellOverflow = K; }
                 else {
                     K = std::max(K, 1);
                     const size_t n = (size_t)std::max<long>(1, A.N);
@@ -945,6 +953,71 @@ struct ArapOps : EnergyOps<T> {
             return true;
         }
         return false;
+    }
+    // ---- the whole linear solve in ONE workgroup (arap_onchip.h; solver parameter amd_onchip = 5): symmetric graphs within the ELL width whose vertices fit a variant ----
+    OnchipGuard ocGuard;      // the switches (OPT_AMD_ONCHIP = 0) and the failure word of the guarded update -- one this kernel never sets: it has no wait that could time out
+    struct AoOffer { int v = 0; const void* fn = nullptr; size_t lds = 0; };
+    std::vector<AoOffer> aoOffers[2];      // [Gauss-Newton, Levenberg-Marquardt]: the variants this device can hold, smallest first
+    bool aoReady = false;
+    void aoInit() {
+        if (aoReady) return;
+        aoReady = true;
+        for (const AoVariant& v : aoVariants<T>())
+            for (int m = 0; m < 2; ++m) {
+                const void* fn = m ? v.lm : v.gn;
+                if (!fn) continue;
+                const size_t lds = (size_t)v.v * kAoMaxBlock * v.ldsPerVertex;
+                hipFuncAttributes fa{};
+                if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.localSizeBytes != 0) { (void)hipGetLastError(); continue; }      // (no scratch in a kernel that is all latency)
+                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); continue; }      // (a variant the device cannot hold is not offered)
+                aoOffers[m].push_back({v.v, fn, v.ldsPerVertex});
+            }
+    }
+    long aoMaxVertices(bool lmv) { aoInit(); return aoOffers[lmv].empty() ? 0 : (long)aoOffers[lmv].back().v * kAoMaxBlock; }
+    // THE predicate of the path: nullptr (on chip, *pick = the variant) or why the plan streams.  pcgSolveOnChip and describe() both ask here.
+    const char* aoWhyNot(int L, bool lmv, const OnChipLm<T>* lm, const AoOffer** pick = nullptr) {
+        if (ocGuard.whyOff()) return ocGuard.whyOff();
+        if (this->onChipLevel < 5) return "amd_onchip=5 was not set";
+        if (this->slab.active) return "row slabs";
+        if (!useGather || !useSym) return "the plane gather is switched off";
+        if (!symGraph) return ellOverflow ? "a vertex has more than 16 neighbours" : "asymmetric graph";
+        if (L <= 0) return "no PCG iterations";
+        if (lmv && lm && !lm->CtC) return "no LM diagonal";
+        aoInit();
+        for (const AoOffer& o : aoOffers[lmv])
+            if (A.N <= (long)o.v * kAoMaxBlock) { if (pick) *pick = &o; return nullptr; }
+        return "too many vertices";
+    }
+    bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
+        const AoOffer* o = nullptr;
+        if (aoWhyNot(L, lm != nullptr, lm, &o) || !this->onChipPre || (lm && !lm->CtC)) return false;
+        const int threads = std::max(1, divUp(divUp(A.N, o->v), kWave)) * kWave;      // only the waves the vertex count needs
+        ArapOcArgs<T> K{A, planes, r0, p0, this->onChipPre, delta, L, traceDev, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0), lm ? lm->resetPeriod : 0, lm ? lm->breakInfo : nullptr};
+        void* kargs[] = {(void*)&K};
+        ocGuard.allocWords(ctx.stream);
+        {
+            ScopedKernel k(ctx, "PCGSolveOnChip");
+            if (hipLaunchKernel(o->fn, dim3(1), dim3(threads), kargs, (size_t)threads * o->v * o->lds, ctx.stream) != hipSuccess) { (void)hipGetLastError(); ocGuard.enabled = false; return false; }
+        }
+        if (!lm) {      // PCGLinearUpdate X += delta, guarded as ocApplyDelta guards it (LM: the solver applies the update itself)
+            ScopedKernel k(ctx, "PCGLinearUpdate");
+            for (size_t i = 0; i < this->unknowns.size(); ++i) {
+                const auto& u = this->unknowns[i];
+                const long cnt = u.elems * u.channels;
+                ocApplyDelta<T><<<(int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, 64)), kBlock, 0, ctx.stream>>>(unknownPtr((int)i), delta + u.offset, cnt, ocGuard.bad, ocGuard.hostErr);
+            }
+        }
+        ocGuard.launched = true;
+        return true;
+    }
+    OnchipGuard* onChipGuard() override { return &ocGuard; }
+    std::string describe(int L, bool lmv, const OnChipLm<T>* lm) override {      // ("key=value; ..." -- no ';' inside a value)
+        const AoOffer* o = nullptr;
+        const char* why = aoWhyNot(L, lmv, lm, &o);
+        char buf[400];
+        if (!why) snprintf(buf, sizeof buf, "path=on-chip; workgroups=1; vertices=%ld; ell=%d; variant=arap_onchipPcg<%s, %d, %s>", A.N, planes.K, sizeof(T) == 4 ? "float" : "double", o->v, lmv ? "LM" : "GN");
+        else snprintf(buf, sizeof buf, "path=launch-per-iteration; why_not_on_chip=%s%s", why, !strcmp(why, "too many vertices") ? (" (the variants serve up to " + std::to_string(aoMaxVertices(lmv)) + ")").c_str() : "");
+        return buf;
     }
     void evalModelCost(const T* delta, Reduction& out, LaunchCtx& ctx) override {
         const int gv = vgrid(), ge = edgeGrid(A.nE, cus);

@@ -1,12 +1,18 @@
 // The mesh energies served by the graph functor engine (graph_engine.h): cotangent_mesh_smoothing, embedded_mesh_deformation,
 // robust_nonrigid_alignment -- the three graph examples of the reference beyond ARAP.  Each functor restates the residuals of its
 // reference .t once, against a scalar type S that the engine instantiates as T or as a dual number.
+// No fused multiply-adds in this file: cot() forms 1 - cos^2 of two unit vectors as dot * dot - ab * ab, and fusing one of the two products moves that difference by an
+// ulp of 1, i.e. by 4e-4 of a sliver triangle's discriminant of 1.6e-4 -- float stages of cotangent on the raptor mesh were 4e-4 .. 7e-4 from the oracle (plain arithmetic).
+#pragma clang fp contract(off)
 #include "graph_engine.h"
 
 namespace optamd {
 namespace {
 
 template <class S> __device__ __forceinline__ S dot3(const S* a, const S* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+// a / b as the dual numbers form their value (a * (1 / b), stencil_engine.h operator/): the cost pass (S = T) then computes the bits of the J^T F pass's residuals
+template <class T> __device__ __forceinline__ T quotient(T a, T b) { return a * (T(1) / b); }
+template <class T, int N> __device__ __forceinline__ Dual<T, N> quotient(const Dual<T, N>& a, const Dual<T, N>& b) { return a / b; }
 
 // ------------------------------------------------------------------------------------------------------------------
 // examples/cotangent_mesh_smoothing/cotangent_mesh_smoothing.t:1-33.  X float3 per vertex; fit w_fit (X - A); per half-edge
@@ -34,13 +40,13 @@ struct CotangentG {
     template <class S> __device__ __forceinline__ static void normalized(const S* p, const S* q, S* out) {      // normalize(p - q), lib.t:54-56
         S d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
         const S len = sqrt(dot3(d, d));
-        out[0] = d[0] / len; out[1] = d[1] / len; out[2] = d[2] / len;
+        out[0] = quotient(d[0], len); out[1] = quotient(d[1], len); out[2] = quotient(d[2], len);
     }
     template <class S> __device__ __forceinline__ static S cot(const S* u, const S* w) {                        // cotangent_mesh_smoothing.t:15-20
         const S ab = dot3(u, w);
         S disc = dot3(u, u) * dot3(w, w) - ab * ab;
         disc = valueOf(disc) > T(0) ? disc : S(T(0.0001));
-        return ab / sqrt(disc);
+        return quotient(ab, sqrt(disc));
     }
     template <class S, class C> __device__ __forceinline__ void edgeResiduals(const C& Xc, long, S* r) const {
         S x[4][3];

@@ -363,13 +363,19 @@ def _half_edges_from_rings(rings):
 
 
 def cotangent_mesh_smoothing(nx, ny=None, double=False, seed=0, noise=0.05):
+    """examples/cotangent_mesh_smoothing/src/CombinedSolver.h:16-44, 68-113 on a procedural torus (closed, like the example's meshes: no
+    hyperedge lists a vertex twice); see cotangent_from_mesh."""
+    V, F = torus_mesh(nx, ny or nx, seed)
+    return cotangent_from_mesh(V, F, double=double, seed=seed, noise=noise)
+
+
+def cotangent_from_mesh(V, F, double=False, seed=0, noise=0.05):
     """examples/cotangent_mesh_smoothing/src/CombinedSolver.h:16-44, 68-113: X = A = the (noisy) input vertices; one hyperedge per
     (vertex, ring neighbour): v0 = vertex, v1 = neighbour, v2 / v3 = previous / next neighbour in the ring (cyclic);
-    w_fit = 1, w_reg = 0.5 (main.cpp:34-35)."""
+    w_fit = 1, w_reg = 0.5 (main.cpp:34-35).  On an open mesh the ring of a valence-2 corner gives v2 == v3."""
     from . import io
-    ny = ny or nx
     ft = np.float64 if double else np.float32
-    V, F = torus_mesh(nx, ny, seed)          # closed, like the example's meshes: no hyperedge lists a vertex twice
+    V = np.asarray(V, dtype=np.float64)
     V = V + np.random.default_rng(seed + 1).normal(0, noise, size=V.shape)
     rings = io.mesh_vertex_rings(len(V), F)
     v0, v1, v2, v3 = [], [], [], []
@@ -384,32 +390,43 @@ def cotangent_mesh_smoothing(nx, ny=None, double=False, seed=0, noise=0.05):
 
 
 def embedded_mesh_deformation(nx, ny=None, double=False, seed=0, perturb=0.0):
-    """examples/embedded_mesh_deformation/src/CombinedSolver.h:33-56, 95-160: Offset = UrShape = node positions, RotMatrix = identity,
-    Constraints = -inf except handle nodes (one edge column pinned, the opposite one lifted); weights 3 / 12 / 5."""
-    from . import io
+    """examples/embedded_mesh_deformation/src/CombinedSolver.h:33-56, 95-160 on a procedural height-field patch: one edge column pinned, the
+    opposite one lifted; see embedded_from_mesh."""
     ny = ny or nx
-    ft = np.float64 if double else np.float32
     V, F = grid_surface_mesh(nx, ny, seed)
+    return embedded_from_mesh(V, F, np.arange(ny) * nx, np.arange(ny) * nx + nx - 1, double=double, seed=seed, perturb=perturb)
+
+
+def embedded_from_mesh(V, F, pinned, lifted, double=False, seed=0, perturb=0.0, lift=(0.0, 0.3, 0.8)):
+    """examples/embedded_mesh_deformation/src/CombinedSolver.h:33-56, 95-160: Offset = UrShape = node positions, RotMatrix = identity,
+    Constraints = -inf except handle nodes (`pinned` stay, `lifted` move by `lift`); weights 3 / 12 / 5."""
+    from . import io
+    ft = np.float64 if double else np.float32
+    V = np.asarray(V, dtype=np.float64)
     rng = np.random.default_rng(seed + 2)
     heads, tails = _half_edges_from_rings(io.mesh_vertex_rings(len(V), F))
     off = V + (rng.normal(0, perturb, size=V.shape) if perturb > 0 else 0)
     rot = np.tile(np.eye(3).reshape(-1), (len(V), 1)) + (rng.normal(0, perturb, size=(len(V), 9)) if perturb > 0 else 0)
     cons = np.full(V.shape, -np.inf)
-    left, right = np.arange(ny) * nx, np.arange(ny) * nx + nx - 1
-    cons[left] = V[left]; cons[right] = V[right] + np.array([0.0, 0.3, 0.8])
+    cons[pinned] = V[pinned]; cons[lifted] = V[lifted] + np.array(lift)
     return Problem("embedded_mesh_deformation", (len(V),),
                    [np.float32(np.sqrt(3.0)), np.float32(np.sqrt(12.0)), np.float32(np.sqrt(5.0)), off.astype(ft), rot.astype(ft), V.astype(ft), cons.astype(ft),
                     np.array(len(heads), dtype=np.int32), heads, tails], (3, 4), double, {"n_edges": int(len(heads))})
 
 
 def robust_nonrigid_alignment(nx, ny=None, double=False, seed=0, perturb=0.0):
+    """examples/robust_nonrigid_alignment/src/CombinedSolver.h:150-180 on a procedural height-field patch; see robust_from_mesh."""
+    V, F = grid_surface_mesh(nx, ny or nx, seed)
+    return robust_from_mesh(V, F, double=double, seed=seed, perturb=perturb)
+
+
+def robust_from_mesh(V, F, double=False, seed=0, perturb=0.0):
     """examples/robust_nonrigid_alignment/src/CombinedSolver.h:150-180: Offset = UrShape = source vertices, Angle = 0, RobustWeights = 1,
     Constraints / ConstraintNormals = the corresponding point and normal on the target surface where a correspondence exists
     (-inf otherwise); w_fit = 10, w_reg = 64 (its starting value)."""
     from . import io
-    ny = ny or nx
     ft = np.float64 if double else np.float32
-    V, F = grid_surface_mesh(nx, ny, seed)
+    V = np.asarray(V, dtype=np.float64)
     rng = np.random.default_rng(seed + 3)
     heads, tails = _half_edges_from_rings(io.mesh_vertex_rings(len(V), F))
     target = V + np.stack([0.05 * np.sin(V[:, 1]), 0.04 * np.cos(V[:, 0]), 0.3 + 0.1 * np.sin(0.5 * V[:, 0])], -1)

@@ -1,0 +1,302 @@
+"""Case builders of the graph-shape tests (test_graph_cases_cpu.py, test_graph_shapes_gpu.py): the four mesh energies on real irregular meshes,
+and transforms that turn a head-grouped generated graph into the other legal inputs of the C API -- any hyperedge order, a hub, a vertex without
+hyperedges, a vertex that is only ever a tail, repeated half-edges.  Every transform returns a new Problem and leaves its input alone; every
+index stays in range and every edge count positive."""
+import os
+
+import numpy as np
+
+from opt_amd import io, workloads as wl
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+ENERGIES = ("cotangent", "embedded", "robust", "arap")
+FUNCTOR_ENERGIES = ("cotangent", "embedded", "robust")      # graph_engine.h; ARAP has its own kernel set (energy_graph.hip)
+STEM = {"cotangent": "cotangent_mesh_smoothing", "embedded": "embedded_mesh_deformation", "robust": "robust_nonrigid_alignment", "arap": "arap_mesh_deformation"}
+# binding slots per .t file: the host edge count, the index arrays (slot 0 = head), the per-vertex arrays, and among those the constraint arrays
+LAYOUT = {
+    "cotangent_mesh_smoothing": dict(count=4, idx=(5, 6, 7, 8), vertex=(2, 3), cons=()),
+    "embedded_mesh_deformation": dict(count=7, idx=(8, 9), vertex=(3, 4, 5, 6), cons=(6,)),
+    "robust_nonrigid_alignment": dict(count=8, idx=(9, 10), vertex=(2, 3, 4, 5, 6, 7), cons=(6,)),
+    "arap_mesh_deformation": dict(count=6, idx=(7, 8), vertex=(2, 3, 4, 5), cons=(5,)),
+}
+
+
+def layout(P):
+    return LAYOUT[P.energy]
+
+
+def index_arrays(P):
+    return [np.asarray(P.params[s]) for s in layout(P)["idx"]]
+
+
+def n_vertices(P):
+    return int(P.dims[0])
+
+
+def _with_indices(P, cols):
+    """A clone of P whose index arrays are `cols` (one int32 array per slot) and whose edge count matches."""
+    Q = P.clone()
+    L = layout(P)
+    for s, c in zip(L["idx"], cols):
+        Q.params[s] = np.ascontiguousarray(np.asarray(c, dtype=np.int32))
+    n = len(Q.params[L["idx"][0]])
+    assert n >= 1 and all(len(Q.params[s]) == n for s in L["idx"])
+    assert all(0 <= int(Q.params[s].min()) and int(Q.params[s].max()) < n_vertices(Q) for s in L["idx"])
+    Q.params[L["count"]] = np.array(n, dtype=np.int32)
+    Q.meta["n_edges"] = n
+    return Q
+
+
+# ---- meshes -------------------------------------------------------------------------------------------------------------------------------------------------
+def armadillo(sub=False):
+    """tests/golden/meshes/armadillo_mesh.npz: 130 vertices, 768 half-edges, valence 3..10, closed (sub: its subdivision, 386 vertices)."""
+    z = np.load(os.path.join(_HERE, "golden", "meshes", "armadillo_mesh.npz"))
+    return z["vertices" + ("_sub" if sub else "")].astype(np.float64), z["faces" + ("_sub" if sub else "")].tolist()
+
+
+def raptor():
+    """tests/fixtures/raptor2k_mesh.npz: 2000 vertices, 12108 half-edges, valence 3..12, closed: several workgroups in every kernel."""
+    z = np.load(os.path.join(_HERE, "fixtures", "raptor2k_mesh.npz"))
+    return z["vertices"].astype(np.float64), z["faces"].tolist()
+
+
+def open_patch():
+    """A 7 x 5 height-field patch (open: 35 vertices, 164 hyperedges); its two valence-2 corners give four cotangent hyperedges with v2 == v3."""
+    return wl.grid_surface_mesh(7, 5, seed=4)
+
+
+def mean_edge_length(V, F):
+    V = np.asarray(V, dtype=np.float64); F = np.asarray(F)
+    return float(np.mean([np.linalg.norm(V[F[:, i]] - V[F[:, (i + 1) % 3]], axis=1).mean() for i in range(3)]))
+
+
+def mesh_problem(energy, V, F, double=False, seed=0, perturb=0.0):
+    """One of the four mesh problems on the triangle mesh (V, F), parameters laid out by the workloads module's own *_from_mesh functions.
+    `perturb` is in units of the mean edge length for positions and in radians / plain units for angles, rotation entries and robust weights.
+    embedded / robust: the mesh is scaled to unit mean edge length (the generators' handle displacements and target surface assume a unit lattice);
+    cotangent / ARAP: raw vertices.  Handles (embedded, ARAP): the 5 % of vertices with the smallest x stay, the 5 % with the largest x move."""
+    V = np.asarray(V, dtype=np.float64)
+    L = mean_edge_length(V, F)
+    order = np.argsort(V[:, 0], kind="stable")
+    k = max(1, len(V) // 20)
+    pinned, lifted = np.sort(order[:k]), np.sort(order[-k:])
+    if energy == "cotangent":
+        return wl.cotangent_from_mesh(V, F, double=double, seed=seed, noise=perturb * L)
+    if energy == "embedded":
+        return wl.embedded_from_mesh(V / L, F, pinned, lifted, double=double, seed=seed, perturb=perturb)
+    if energy == "robust":
+        return wl.robust_from_mesh(V / L, F, double=double, seed=seed, perturb=perturb)
+    assert energy == "arap", energy
+    pos = np.concatenate([V[pinned], V[lifted] + L * np.array([0.0, 0.5, 1.0])])
+    P = io.arap_problem_from_mesh(V, F, np.concatenate([pinned, lifted]), pos, double=double, alpha=1.0)
+    if perturb > 0:
+        rng = np.random.default_rng(seed)
+        ft = P.params[2].dtype
+        P.params[2] = (P.params[2].astype(np.float64) + perturb * L * rng.standard_normal(V.shape)).astype(ft)
+        P.params[3] = (perturb * rng.standard_normal(V.shape)).astype(ft)
+    return P
+
+
+# ---- cotangent weights in numpy (the .t's expressions in double): what the margin tests and the hub / tail builders look at -----------------------------------
+def cotangent_terms(X, v0, v1, v2, v3):
+    """(weight before its guard, the smaller of the two discriminants) per hyperedge: cotangent_mesh_smoothing.t:22-33."""
+    X = np.asarray(X, dtype=np.float64)
+
+    def unit(p, q):
+        d = X[p] - X[q]
+        return d / np.linalg.norm(d, axis=1, keepdims=True)
+
+    def cot(a, b):
+        c = np.sum(a * b, 1)
+        disc = np.sum(a * a, 1) * np.sum(b * b, 1) - c * c
+        return c / np.sqrt(np.where(disc > 0, disc, 0.0001)), disc
+
+    ca, da = cot(unit(v0, v2), unit(v1, v2))
+    cb, db = cot(unit(v0, v3), unit(v1, v3))
+    return 0.5 * (ca + cb), np.minimum(da, db)
+
+
+def cotangent_margins(P):
+    """(min |w|, min disc, share of hyperedges on the w <= 0 branch) of a cotangent problem at its start."""
+    w, disc = cotangent_terms(P.params[2], *index_arrays(P))
+    return float(np.abs(w).min()), float(disc.min()), float(np.mean(w <= 0))
+
+
+# ---- transforms -----------------------------------------------------------------------------------------------------------------------------------------------
+def edge_permutation(heads, how, seed=0):
+    heads = np.asarray(heads)
+    n = len(heads)
+    if how == "shuffle":
+        return np.random.default_rng(seed).permutation(n)
+    if how == "reverse":
+        return np.arange(n)[::-1].copy()
+    if how == "interleave":      # round-robin over heads: all first hyperedges of every head, then all second ones, ...
+        order = np.argsort(heads, kind="stable")
+        rank = np.empty(n, dtype=np.int64)
+        sorted_heads = heads[order]
+        start = np.r_[0, np.flatnonzero(np.diff(sorted_heads)) + 1]
+        run = np.repeat(start, np.diff(np.r_[start, n]))
+        rank[order] = np.arange(n) - run
+        return np.lexsort((heads, rank))
+    raise ValueError(how)
+
+
+def reorder(P, how, seed=0):
+    """The same graph with its hyperedges in another order: ONE permutation applied to all index arrays together."""
+    cols = index_arrays(P)
+    perm = edge_permutation(cols[0], how, seed)
+    return _with_indices(P, [c[perm] for c in cols])
+
+
+def _grouped(cols):
+    """Stable sort by head: added hyperedges join the run of their head."""
+    order = np.argsort(np.asarray(cols[0]), kind="stable")
+    return [np.asarray(c)[order] for c in cols]
+
+
+def _ring_pair(cols, v, avoid):
+    """Two distinct neighbours of v (tails of its half-edges) other than `avoid`: the v2 / v3 of an added cotangent hyperedge at v."""
+    nb = [int(t) for t in np.asarray(cols[1])[np.asarray(cols[0]) == v] if int(t) != avoid]
+    nb = list(dict.fromkeys(nb))
+    return (nb[0], nb[1]) if len(nb) >= 2 else None
+
+
+def with_hub(P, degree, hub=None):
+    """One vertex joined to further vertices until it heads `degree` half-edges, every added half-edge with its reverse; the graph stays grouped by head.
+    cotangent: the hyperedge (hub, v) and its reverse take v's first two ring neighbours as v2 / v3, and only candidates v whose weights keep the
+    guards' margins (|w|, disc >= 1e-3) are taken, so the added hyperedges cannot flip a branch between two correct implementations."""
+    cols = [c.copy() for c in index_arrays(P)]
+    N = n_vertices(P)
+    h = N // 2 if hub is None else hub
+    have = {int(t) for t in cols[1][cols[0] == h]}
+    need = degree - int(np.sum(cols[0] == h))
+    assert need > 0, "the hub already has that many half-edges"
+    add = [[] for _ in cols]
+    for v in range(N):
+        if need == 0:
+            break
+        if v == h or v in have:
+            continue
+        if len(cols) == 4:
+            pair = _ring_pair(cols, v, h)
+            if pair is None or h in pair:
+                continue
+            cand = np.array([[h, v, pair[0], pair[1]], [v, h, pair[0], pair[1]]])
+            w, disc = cotangent_terms(P.params[2], *cand.T)
+            if np.abs(w).min() < 1e-3 or disc.min() < 1e-3:
+                continue
+            for row in cand:
+                for j in range(4):
+                    add[j].append(int(row[j]))
+        else:
+            add[0] += [h, v]; add[1] += [v, h]
+        need -= 1
+    assert need == 0, "not enough candidates for the hub"
+    Q = _with_indices(P, _grouped([np.concatenate([c, np.array(a, dtype=np.int32)]) for c, a in zip(cols, add)]))
+    assert int(np.sum(Q.params[layout(Q)["idx"][0]] == h)) == degree
+    Q.meta["hub"] = h
+    return Q
+
+
+def _append_vertex(P, position):
+    """A clone with one more vertex: rest and current position `position`, no constraint (-inf), zero angle, identity rotation, unit robust weight."""
+    Q = P.clone()
+    L = layout(P)
+    N = n_vertices(P)
+    for s in L["vertex"]:
+        a = np.asarray(Q.params[s])
+        row = np.zeros((1,) + a.shape[1:], dtype=a.dtype)
+        Q.params[s] = np.ascontiguousarray(np.concatenate([a, row]))
+    pos = np.asarray(position, dtype=np.float64)
+    e = P.energy
+    if e == "cotangent_mesh_smoothing":
+        Q.params[2][N] = pos; Q.params[3][N] = pos
+    elif e == "embedded_mesh_deformation":
+        Q.params[3][N] = pos; Q.params[4][N] = np.eye(3).reshape(-1); Q.params[5][N] = pos
+    elif e == "robust_nonrigid_alignment":
+        Q.params[2][N] = pos; Q.params[4][N] = 1.0; Q.params[5][N] = pos; Q.params[7][N] = (0.0, 0.0, 1.0)
+    else:
+        Q.params[2][N] = pos; Q.params[4][N] = pos
+    for s in L["cons"]:
+        Q.params[s][N] = -np.inf
+    Q.dims = (N + 1,)
+    return Q
+
+
+def _rest_positions(P):
+    return np.asarray(P.params[{"cotangent_mesh_smoothing": 3, "embedded_mesh_deformation": 5, "robust_nonrigid_alignment": 5, "arap_mesh_deformation": 4}[P.energy]], dtype=np.float64)
+
+
+def with_isolated_vertex(P):
+    """One more vertex that no hyperedge names (empty incidence list; for the constrained energies a zero preconditioner diagonal): the vertex count becomes odd."""
+    R = _rest_positions(P)
+    Q = _append_vertex(P, R.mean(0) + 0.5 * R.std(0))
+    assert n_vertices(Q) % 2 == 1
+    return Q
+
+
+def with_tail_only_vertex(P, heads=(3, 11, 40)):
+    """One more vertex that appears only in slot 1 (it heads nothing): half-edges from three existing vertices, without their reverses -- an asymmetric graph.
+    cotangent: v2 / v3 of the added hyperedge at head u are u's first two ring neighbours; the new vertex sits off the surface near u's ring so that the
+    guards' margins hold (the CPU tests assert them)."""
+    cols = [c.copy() for c in index_arrays(P)]
+    N = n_vertices(P)
+    R = _rest_positions(P)
+    nb = np.unique(np.concatenate([cols[1][cols[0] == u] for u in heads]))
+    span = np.linalg.norm(R[nb] - R[nb].mean(0), axis=1).mean()
+    Q = _append_vertex(P, R[nb].mean(0) + span * np.array([0.31, -0.47, 0.83]))
+    add = [[] for _ in cols]
+    for u in heads:
+        add[0].append(u); add[1].append(N)
+        if len(cols) == 4:
+            a, b = _ring_pair(cols, u, N)
+            add[2].append(a); add[3].append(b)
+    Q = _with_indices(Q, _grouped([np.concatenate([c, np.array(a, dtype=np.int32)]) for c, a in zip(cols, add)]))
+    idx = index_arrays(Q)
+    assert not np.any(idx[0] == N) and np.sum(idx[1] == N) == len(heads)
+    Q.meta["tail_only"] = N
+    return Q
+
+
+def with_duplicate_edges(P, k, seed=0):
+    """k half-edges repeated together with their reverses (whole hyperedges for cotangent), appended after the grouped list."""
+    cols = [c.copy() for c in index_arrays(P)]
+    n = len(cols[0])
+    pick = np.random.default_rng(seed).choice(n, size=k, replace=False)
+    rows = []
+    for e in pick:
+        rev = np.flatnonzero((cols[0] == cols[1][e]) & (cols[1] == cols[0][e]))
+        assert len(rev) >= 1, "the graph carries every half-edge in both directions"
+        rows += [int(e), int(rev[0])]
+    rows = np.array(rows)
+    return _with_indices(P, [np.concatenate([c, c[rows]]) for c in cols])
+
+
+def without_one_reverse_edge(P, e=5):
+    """The graph minus half-edge e (its reverse stays): asymmetric, one half-edge shorter."""
+    cols = index_arrays(P)
+    keep = np.ones(len(cols[0]), dtype=bool); keep[e] = False
+    return _with_indices(P, [c[keep] for c in cols])
+
+
+def max_out_degree(P):
+    return int(np.bincount(index_arrays(P)[0], minlength=n_vertices(P)).max())
+
+
+# ---- the inputs the tests share -------------------------------------------------------------------------------------------------------------------------------
+PERTURB = {"cotangent": 0.0, "embedded": 0.03, "robust": 0.03, "arap": 0.02}      # (cotangent: see COTANGENT_INPUTS -- its noise decides the guards' margins)
+# (mesh, perturb in mean edge lengths, seed) of the cotangent inputs; test_graph_cases_cpu.py asserts the guards' margins of each
+# (raptor: noise of 0.02 mean edge lengths drawn from default_rng(seed + 1 = 3); the draws of default_rng(2) and default_rng(4) leave |w| below 1e-4 and are not used)
+COTANGENT_INPUTS = {"armadillo": (0.0, 0), "armadillo_sub": (0.0, 0), "raptor": (0.02, 2), "open_patch": (None, 4)}
+_MESHES = {"armadillo": armadillo, "armadillo_sub": lambda: armadillo(sub=True), "raptor": raptor, "open_patch": open_patch}
+
+
+def base_problem(energy, mesh, double):
+    """The ordered (head-grouped) problem of `energy` on `mesh` that every reordered / re-shaped case starts from."""
+    V, F = _MESHES[mesh]()
+    if energy == "cotangent":
+        perturb, seed = COTANGENT_INPUTS[mesh]
+        if mesh == "open_patch":
+            return wl.cotangent_from_mesh(V, F, double=double, seed=seed, noise=0.05)
+        return mesh_problem(energy, V, F, double=double, seed=seed, perturb=perturb)
+    return mesh_problem(energy, V, F, double=double, seed=7, perturb=PERTURB[energy])

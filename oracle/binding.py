@@ -64,6 +64,7 @@ def lib():
         L.OptOracle_GetCostHistory.argtypes = [vp, vp]
         L.OptOracle_TrustRegionRadius.restype = cd
         L.OptOracle_TrustRegionRadius.argtypes = [vp]
+        L.OptOracle_GetLastDecision.argtypes = [vp, vp]
         L.OptOracle_PoissonPatchSolve.argtypes = [ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp]
         _lib = L
     return _lib
@@ -175,6 +176,12 @@ class OracleSolver:
 
     def trust_region_radius(self):
         return lib().OptOracle_TrustRegionRadius(self._h)
+
+    def last_decision(self):
+        """(prevCost, newCost, model_cost_change, radius_decrease_factor): what the last LM step's accept / reject test compared, and the decrease factor it left."""
+        out = np.zeros(4, dtype=np.float64)
+        lib().OptOracle_GetLastDecision(self._h, out.ctypes.data)
+        return tuple(float(v) for v in out)
 
 
 def poisson_patch_solve(X, T, M, n_iterations, l_iterations, patch_iterations=16, patch_size=32):

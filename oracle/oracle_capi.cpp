@@ -83,6 +83,12 @@ void OptOracle_SetReduction(void* hv, int mode, unsigned seed) {
 // Process-wide: which float sin / cos the restatement evaluates (dual.hpp trigSeed: 0 = the host libm; n > 0 = a seeded implementation within 1 ulp)
 void OptOracle_SetTrigVariant(unsigned seed) { oracle::trigSeed() = seed; }
 void OptOracle_SetThreads(void* hv, int n) { auto* h = (Handle*)hv; if (h->dbl) h->sd->threads = n; else h->sf->threads = n; }
+// out[0..3]: prevCost, newCost, model_cost_change of the last LM step's accept / reject test, and the radius_decrease_factor it left
+void OptOracle_GetLastDecision(void* hv, double* out) {
+    auto* h = (Handle*)hv;
+    for (int i = 0; i < 3; ++i) out[i] = h->dbl ? h->sd->lastDecision[i] : h->sf->lastDecision[i];
+    out[3] = h->dbl ? (double)h->sd->radius_decrease_factor : (double)h->sf->radius_decrease_factor;
+}
 long OptOracle_NumUnknownScalars(void* hv) { auto* h = (Handle*)hv; return h->dbl ? h->ed->nScalars : h->ef->nScalars; }
 
 // --- probes -------------------------------------------------------------------------------------

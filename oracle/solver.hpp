@@ -114,6 +114,7 @@ struct Solver {
     // LM state lives in pd.parameters as opt_float (o.t:933-938, solver.t:998-1001)
     T trust_region_radius = 0, radius_decrease_factor = 0, min_lm_diagonal = 0, max_lm_diagonal = 0;
     T prevCost = 0;
+    double lastDecision[3] = {0, 0, 0};   // what the last LM step's accept / reject test compared: prevCost, newCost, model_cost_change (a probe for the tests of the outer-loop controls)
     std::vector<T> delta, r, b, Adelta, z, p, Ap_X, CtC, preconditioner, SSq, prevX;
     std::vector<char> active;
     T aNum = 0, aDen = 0, bNum = 0, q = 0;
@@ -522,6 +523,7 @@ struct Solver {
         if (lm) {
             T cost_change = prevCost - newCost;
             T relative_decrease = cost_change / model_cost_change;
+            lastDecision[0] = (double)prevCost; lastDecision[1] = (double)newCost; lastDecision[2] = (double)model_cost_change;
             if (cost_change >= 0 && relative_decrease > min_relative_decrease) {
                 T absolute_function_tolerance = prevCost * function_tolerance;
                 if (cost_change <= absolute_function_tolerance) { costHistory.push_back((double)prevCost); return 0; }

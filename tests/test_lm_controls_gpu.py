@@ -10,6 +10,9 @@ side by side with the CPU oracle, which follows the reference's order literally:
   * image_warping float + double (single-kernel LM loop of energy_image_warping.hip), shape_from_shading double (energy_sfs.hip), and
     poisson_image_editing (no single-kernel LM loop: the generic Step1/Step2 path of solver.hip).
 Costs after every outer step, the trust-region radius and the final unknowns must agree (double 1e-10 / 1e-8 / 1e-9; float 1e-5 on costs).
+
+The OUTER-loop controls -- function_tolerance, min / max_trust_region_radius, radius_decrease_factor, min / max_lm_diagonal, when each takes effect -- are tested on every
+LM path by tests/test_lm_outer_controls_gpu.py (cases: tests/lm_control_cases.py, proved on the oracle alone by tests/test_lm_control_cases_cpu.py).
 """
 import numpy as np
 import pytest

@@ -91,7 +91,7 @@ int OptAmd_PlanOnChipStatus(Opt_Plan* plan);
 int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
 
 /* Solver parameters of this build, set through the reference's own Opt_SetSolverParameter (a reference build only warns about names it does not know,
- * solverGPUGaussNewton.t:1205-1221, so a caller that sets them stays portable); both are `int*`:
+ * solverGPUGaussNewton.t:1205-1221, so a caller that sets them stays portable); all are `int*`:
  *   "amd_reference_order"  1: every PCG iteration runs the reference's own sequence PCGStep1; PCGStep2; PCGStep3 (solverGPUGaussNewton.t:1056-1092) on kernels that keep
  *                          r, z and A p in memory and form the three sums as the reference does (beta numerator = r.z directly).  This is the loop that meets the 1e-5
  *                          (float) contract against the oracle at every horizon tested (400 PCG iterations included); it moves the reference formulation's 180 B/pixel
@@ -113,6 +113,20 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          (the reference's own meshes: small_armadillo 130 / 386 vertices, head 689).  Any other graph keeps the two launches per PCG iteration, and
  *                          OptAmd_PlanDescribe says why (why_not_on_chip).  The kernel has no grid-wide wait and therefore no time-out path.  Under 0-4 and by default
  *                          the mesh energies keep their bits.  Opt-in for the same reason as 2-4.
+ *   "amd_graph_fused"      0 (default): nothing changes.  1: cotangent_mesh_smoothing, embedded_mesh_deformation and robust_nonrigid_alignment (the functor mesh
+ *                          energies, graph_engine.h) run TWO launches per PCG iteration, Gauss-Newton and Levenberg-Marquardt, float and double, where by default they run
+ *                          the reference's sequence in four (PCGStep3, PCGStep1_Graph, PCGStep1, PCGStep2): ge_flatStep (PCGStep2 + PCGStep3 of the previous iteration,
+ *                          beta's numerator by expansion) and ge_gather (PCGStep1: J^T J p per vertex with every (hyperedge, slot) term evaluated in place instead of
+ *                          read from a record the edge pass wrote).  J^T J p itself keeps its bits -- OptAmd_ApplyJTJ under 1 is one launch with the same `out` -- but the
+ *                          loop sums in another order and takes beta's numerator by expansion, so a solve rounds differently: opt-in.  It needs gather mode (the default;
+ *                          OPT_AMD_GRAPH_GATHER=0 or more than 2^31 incidences keep the four launches) and a preconditioned energy; "amd_reference_order" = 1 wins; other
+ *                          energies ignore it.  OptAmd_PlanDescribe then says `launches_per_iteration=2; kernels=ge_flatStep+ge_gather<T, functor, GN|LM>`, or
+ *                          `why_not_fused=` with the reason; with 0 its text is unchanged.  Measured (profiles/graph_fused.md; one MI355X, whole float solves, 0 -> 1,
+ *                          median of 5 alternating, us per PCG iteration): embedded on the reference's 2000-vertex raptor GN 1 x 1000 20.1 -> 17.2, 5 x 125 20.6 -> 17.8,
+ *                          LM 5 x 125 32.2 -> 23.0, at 512 x 512 178.8 -> 80.8; robust raptor GN 10 x 250 20.4 -> 20.1, LM 28.3 -> 24.6, 512 x 512 100.7 -> 83.8;
+ *                          cotangent is SLOWER everywhere (raptor GN 27.4 -> 44.1, LM 33.0 -> 48.9, 512 x 512 115.3 -> 185.4): four slots per hyperedge mean four
+ *                          evaluations of its normalisations and square roots per hyperedge where the edge pass does one.  Set it for embedded_mesh_deformation and
+ *                          robust_nonrigid_alignment, not for cotangent_mesh_smoothing.
  * OptAmd_PlanDescribe reports the choice.  (The environment switches OPT_AMD_ONEKERNEL / OPT_AMD_ONCHIP remain as process-wide development overrides.) */
 
 /* The float4 copy rate of this box in GB/s: `bytes` moved in total per repetition (half read, half written; device memory allocated and freed inside the call),

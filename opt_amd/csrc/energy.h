@@ -188,6 +188,9 @@ struct EnergyOps {
     // on-chip solve depends on the level in Gauss-Newton too, or reads the preconditioner from memory (image_warping with a general UrShape, level 4), finds them here
     int onChipLevel = 1;
     T* onChipPre = nullptr;
+    // The plan's amd_graph_fused, already combined with amd_reference_order == 0 (which wins over every path selection), handed over with onChipLevel: the functor
+    // mesh energies (graph_engine.h) then run two launches per PCG iteration and J^T J p without records; every other kernel set ignores it
+    bool graphFused = false;
     // Row slabs, behind a pcgSolveOnChip launch (which then applies nothing itself): onChipVerdict leaves this rank's verdict (0 fine / 1 failed) in a device scalar, the
     // solver all-reduces it, onChipApply applies X += delta iff the sum is 0 -- every rank keeps its update or none does -- and tells the host (OnchipGuard::failedNow).
     virtual void onChipVerdict(double* /*out*/, bool /*refused*/, LaunchCtx&) {}

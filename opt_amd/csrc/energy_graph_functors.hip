@@ -21,6 +21,8 @@ template <class T, int N> __device__ __forceinline__ Dual<T, N> quotient(const D
 // differentiated like everything else.  UsePreconditioner(true).
 template <class T>
 struct CotangentG {
+    static constexpr const char* kName = "CotangentG";
+    static constexpr bool kSlotAtRunTime = true;
     static constexpr int NIMG = 1, K = 3, V = 4, RV = 3, RE = 3;
     static constexpr __host__ __device__ int imgOf(int) { return 0; }
     static constexpr __host__ __device__ int chOf(int k) { return k; }
@@ -69,6 +71,8 @@ struct CotangentG {
 // (Offset_v1 - Offset_v0) - RotMatrix_v0 (UrShape_v1 - UrShape_v0)  (Matrix3x3Mul, lib.t:39-44).  UsePreconditioner(true).
 template <class T>
 struct EmbeddedG {
+    static constexpr const char* kName = "EmbeddedG";
+    static constexpr bool kSlotAtRunTime = false;
     static constexpr int NIMG = 2, K = 12, V = 2, RV = 9, RE = 3;
     static constexpr __host__ __device__ int imgOf(int k) { return k < 3 ? 0 : 1; }
     static constexpr __host__ __device__ int chOf(int k) { return k < 3 ? k : k - 3; }
@@ -110,6 +114,8 @@ struct EmbeddedG {
 // Per half-edge the ARAP term with Rotate3D (lib.t:77-91).  UsePreconditioner(true).
 template <class T>
 struct RobustG {
+    static constexpr const char* kName = "RobustG";
+    static constexpr bool kSlotAtRunTime = true;
     static constexpr int NIMG = 3, K = 7, V = 2, RV = 6, RE = 3;
     static constexpr __host__ __device__ int imgOf(int k) { return k < 3 ? 0 : k < 6 ? 1 : 2; }
     static constexpr __host__ __device__ int chOf(int k) { return k < 3 ? k : k < 6 ? k - 3 : 0; }

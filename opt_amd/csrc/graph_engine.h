@@ -10,7 +10,9 @@
 // No atomics: unlike the reference's graph kernels (one atomic per (vertex, unknown), unordered) a solve is bit-reproducible.
 // OPT_AMD_GRAPH_GATHER=0 selects the scatter formulation instead (wave-aggregated atomics for the first vertex, whose edges arrive
 // grouped, OptGraph.h:64-76; plain atomics for the others).
-// The functor G provides (constexpr / static): NIMG, K, imgOf(k), chOf(k), channels(img), V, RV, RE, edgeDepends(ri, j);
+// Solver parameter amd_graph_fused = 1: J^T J p as ONE launch that evaluates every record in place (ge_gather: the same bits) and the PCG iteration as two launches
+// (ge_flatStep + ge_gather) through the solver's launch-per-iteration loops, where the default runs the reference's sequence in four.
+// The functor G provides (constexpr / static): NIMG, K, imgOf(k), chOf(k), channels(img), V, RV, RE, edgeDepends(ri, j, k), kName (for OptAmd_PlanDescribe), kSlotAtRunTime (ge_slotDispatch);
 // members N, nE, vidx[V], X[NIMG]; host bindParams(void**), unknownParam(img).
 #pragma once
 #include "stencil_engine.h"
@@ -186,6 +188,172 @@ __global__ __launch_bounds__(kBlock) void ge_edges(G g, const T* __restrict__ ve
     if (MODE != 2) { const double t = blockReduceSum(acc, scratch); if (threadIdx.x == 0 && partials) partials[blockIdx.x] = t; }
 }
 
+// ---- two launches per PCG iteration (solver parameter amd_graph_fused = 1): [ge_flatStep: PCGStep2 + PCGStep3 of iteration k-1] + [ge_gather: PCGStep1 of iteration k] ----
+// unknown k of vertex j of one hyperedge: component 0 = the solver vector, components 1..K = d/d(unknown k of ONE slot) -- where EdgeCtx seeds all V.
+// J >= 0: that slot at compile time (derivative components no residual of the slot depends on fold away); J < 0: the member `slot` at run time (one body for every slot).
+template <class T, class G, int J>
+struct SlotCtx {
+    typedef Dual<T, 1 + G::K> S;
+    const G& g; long vid[G::V]; const T* vec; const GOff<G>& vo; int slot;
+    __device__ __forceinline__ S operator()(int j, int k) const {
+        S r(g.X[G::imgOf(k)][vid[j] * G::channels(G::imgOf(k)) + G::chOf(k)]);
+        r.d[0] = vec[unknownIndex<T, G>(vo, vid[j], k)];
+        if (j == (J >= 0 ? J : slot)) r.d[1 + k] = T(1);
+        return r;
+    }
+};
+// What ge_edges<T, G, 3> writes to the record of (slot, hyperedge e), computed instead of stored: forward-mode components do not interact, so the K derivative
+// components seeded here carry the bits of components 1 + slot K .. of the edge pass.  jp2 (meaningful at slot 0): |J p|^2 of the hyperedge, its share of p . A p.
+template <class T, class G, int J>
+__device__ __forceinline__ void ge_slotRecord(const G& g, const GOff<G>& vo, const T* vec, long e, int slot, T (&q)[G::K], T& jp2) {
+    typedef SlotCtx<T, G, J> Ctx;
+    typedef typename Ctx::S S;
+    const int js = J >= 0 ? J : slot;
+    Ctx X{g, {}, vec, vo, js};
+#pragma unroll
+    for (int j = 0; j < G::V; ++j) X.vid[j] = g.vidx[j][e];
+    S r[G::RE];
+    g.template edgeResiduals<S>(X, e, r);
+    if (J <= 0) { T s = 0; for (int i = 0; i < G::RE; ++i) s += r[i].d[0] * r[i].d[0]; jp2 = s; }
+#pragma unroll
+    for (int k = 0; k < G::K; ++k) {
+        T gk = 0;
+#pragma unroll
+        for (int i = 0; i < G::RE; ++i) {
+            if (!G::edgeDepends(i, js, k)) continue;
+            gk += r[i].d[1 + k] * r[i].d[0];
+        }
+        q[k] = gk;
+    }
+}
+// G::kSlotAtRunTime: the lanes of a wave walk entries of different slots, so V compile-time bodies run one after the other.  A functor whose hyperedge is expensive to
+// evaluate (cotangent: four normalisations and two cotangents; robust: three sines and cosines) takes ONE body with the seeds chosen at run time instead; embedded, whose
+// residuals are linear and whose slot-1 body folds to the three Offset components, keeps the V compile-time bodies.  The bits are the same either way.
+template <class T, class G, int J = 0>
+__device__ __forceinline__ void ge_slotDispatch(int j, const G& g, const GOff<G>& vo, const T* vec, long e, T (&q)[G::K], T& jp2) {
+    if constexpr (G::kSlotAtRunTime) ge_slotRecord<T, G, -1>(g, vo, vec, e, j, q, jp2);
+    else {
+        if (j == J) ge_slotRecord<T, G, J>(g, vo, vec, e, J, q, jp2);
+        else if constexpr (J + 1 < G::V) ge_slotDispatch<T, G, J + 1>(j, g, vo, vec, e, q, jp2);
+    }
+}
+// S.r != nullptr: the launch is the Step1 half of a two-kernel PCG iteration; besides p . A p it sums, at the vertex, alphaNumerator = sum M r^2 and the two sums of
+// the expanded beta numerator, s2 = sum M r . A p and s3 = sum M (A p)^2 (energy.h PcgIterArgs), from the r and M = pre it is handed.
+template <class T> struct GeIterSums { const T* r; const T* M; double *aNum, *s2, *s3; };
+// out = J^T J vec (LM: + CtC vec) without records: ge_vertices<T, G, 3, GE_GATHER_LANES> with every record it would load evaluated in place -- the same lane split,
+// the same ascending walk of the incidence list, the same shuffle fold, hence the same bits in `out`.  The edges' share of p . A p, |J p|^2 per hyperedge, is
+// counted once: at the hyperedge's slot-0 entry.
+template <class T, class G, bool LM>
+__global__ __launch_bounds__(kBlock) void ge_gather(G g, const T* __restrict__ vec, GOff<G> vo, T* __restrict__ out, const T* __restrict__ CtC, double* __restrict__ partials,
+                                                     Incidence inc, GeIterSums<T> S) {
+    constexpr int LANES = GE_GATHER_LANES;
+    __shared__ double scratch[4 * (kBlock / kWave + 1)];
+    double acc = 0, accNum = 0, acc2 = 0, acc3 = 0;
+    const int sub = threadIdx.x % LANES;
+    const int nE = g.nE;
+    for (long v = (blockIdx.x * (long)blockDim.x + threadIdx.x) / LANES; v < g.N; v += (long)gridDim.x * blockDim.x / LANES) {
+        typedef VertexCtx<T, G, true, true> Ctx;
+        typedef typename Ctx::S SV;
+        T gs[G::K];
+        if (sub == 0) {
+            SV r[G::RV > 0 ? G::RV : 1];
+            g.template vertexResiduals<SV>(Ctx{g, v, vec, vo}, v, r);
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) {
+                T gk = 0;
+#pragma unroll
+                for (int i = 0; i < G::RV; ++i) gk += r[i].d[1 + k] * r[i].d[0];
+                const long u = unknownIndex<T, G>(vo, v, k);
+                if (LM) gk += CtC[u] * vec[u];
+                acc += (double)(vec[u] * gk);
+                gs[k] = gk;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) gs[k] = 0;
+        }
+        for (int t = inc.off[v] + sub, te = inc.off[v + 1]; t < te; t += LANES) {
+            const int id = inc.idx[t], j = id / nE;
+            T q[G::K], jp2 = 0;
+            ge_slotDispatch<T, G>(j, g, vo, vec, (long)(id - j * nE), q, jp2);
+            if (j == 0) acc += (double)jp2;
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) gs[k] += q[k];
+        }
+#pragma unroll
+        for (int off = LANES / 2; off > 0; off >>= 1)
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) gs[k] += __shfl_down(gs[k], off, LANES);
+        if (sub == 0) {
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) {
+                const long u = unknownIndex<T, G>(vo, v, k);
+                out[u] = gs[k];
+                if (S.r) {
+                    const double m = (double)S.M[u], rr = (double)S.r[u], a = (double)gs[k];
+                    accNum += (m * rr) * rr; acc2 += (m * rr) * a; acc3 += (m * a) * a;
+                }
+            }
+        }
+    }
+    if (S.r) {
+        double vv[4] = {acc, accNum, acc2, acc3};
+        blockReduceSumN<4>(vv, scratch);
+        if (threadIdx.x == 0) { if (partials) partials[blockIdx.x] = vv[0]; S.aNum[blockIdx.x] = vv[1]; S.s2[blockIdx.x] = vv[2]; S.s3[blockIdx.x] = vv[3]; }
+        return;
+    }
+    const double t = blockReduceSum(acc, scratch);
+    if (threadIdx.x == 0 && partials) partials[blockIdx.x] = t;
+}
+
+// PCGStep2 + PCGStep3 of the previous iteration in one flat pass over the padded scalars, alpha and beta from the previous launch's partial sums (beta's numerator by
+// the expansion of energy.h PcgIterArgs, clamped at 0; the reference's guards, solver.t:456-459, 544-547).  Energy-independent: arap_flatStepPlanes without the planes.
+// LM: delta goes to deltaOut (the solver enqueues the next launch before it has read Q), Q_{k-1} = 1/2 sum delta . (r + b) (solver.t:483-485) leaves as per-workgroup
+// partials (tagged words if qTag != 0), and after a split residual reset (afterReset: delta and r are already the new ones, solver.t:1077-1083) the pass only forms
+// p = M r + beta p with beta = sum bNum / sum bDen.
+template <class T> struct GeLmStep { const T* b; T* deltaOut; double* q; unsigned qTag; int afterReset; const double* bNumP; int nbNum; const double* bDenP; int nbDen; };
+template <class T, bool LM>
+__global__ __launch_bounds__(kBlock) void ge_flatStep(long n, T* __restrict__ delta, const T* __restrict__ pOld, const T* __restrict__ rOld, const T* __restrict__ Ap, const T* __restrict__ M,
+                                                       T* __restrict__ rNew, T* __restrict__ pNew, const double* aNumP, int nNum, const double* aDenP, int nDen,
+                                                       const double* s2P, int n2, const double* s3P, int n3, GeLmStep<T> L) {
+    __shared__ double scratch[4 * (kBlock / kWave + 1)];
+    T alpha, beta;
+    const bool restart = LM && L.afterReset;
+    if (restart) {
+        const double* const ps[2] = {L.bNumP, L.bDenP}; const int ns[2] = {L.nbNum, L.nbDen}; double o2[2];
+        sumPartialsN<2>(ps, ns, scratch, o2);
+        const T bNum = (T)o2[0], bDen = (T)o2[1];
+        alpha = T(0); beta = (bDen > T(0)) ? bNum / bDen : T(0);                            // PCGStep3's guard (solver.t:544-547)
+    } else {
+        const double* const ps[4] = {aNumP, aDenP, s2P, s3P}; const int ns[4] = {nNum, nDen, n2, n3}; double o4[4];
+        sumPartialsN<4>(ps, ns, scratch, o4);
+        const T aNum = (T)o4[0], aDen = (T)o4[1];
+        alpha = (aDen > T(0)) ? aNum / aDen : T(0);                                          // solver.t:456-459
+        const double bNumD = fmax(o4[0] - 2.0 * (double)alpha * o4[2] + (double)alpha * (double)alpha * o4[3], 0.0);
+        beta = (aNum > T(0)) ? (T)bNumD / aNum : T(0);                                       // solver.t:544-547
+    }
+    T* const dOut = LM ? L.deltaOut : delta;
+    double accQ = 0;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const T p = pOld[i], r = rOld[i], m = M[i];
+        T rn, pn;
+        if (restart) { rn = r; pn = m * r + beta * p; }
+        else {
+            const T d = delta[i] + alpha * p;
+            rn = r - alpha * Ap[i];
+            const T z = m * rn;
+            pn = z + beta * p;
+            if (LM) accQ += (double)(T(0.5) * (d * (rn + L.b[i])));
+            dOut[i] = d;
+        }
+        rNew[i] = rn; pNew[i] = pn;
+    }
+    if (LM && L.q && !restart) {
+        const double tq = blockReduceSum(accQ, scratch);
+        if (threadIdx.x == 0) { if (L.qTag) storeTaggedPartial(L.q, blockIdx.x, tq, L.qTag); else L.q[blockIdx.x] = tq; }
+    }
+}
+
 template <class T, class G>
 struct GraphOps : EnergyOps<T> {
     G g{};
@@ -200,7 +368,7 @@ struct GraphOps : EnergyOps<T> {
     }
     int vgrid(int lanes = 1) const { return (int)std::max<long>(1, std::min<long>((g.N * lanes + kBlock - 1) / kBlock, kMaxPartials / 2)); }
     // gather mode state: incidence lists (rebuilt when the graph arrays change: pointers, count or an order-independent checksum) and the record buffer
-    bool useGather = true;
+    bool useGather = true, gatherTooLarge = false;
     int *incOff = nullptr, *incIdx = nullptr, *cursors = nullptr; T* rec = nullptr; long recCapacity = 0;
     void* scanTemp = nullptr; size_t scanTempBytes = 0; unsigned long long* dChecksum = nullptr;
     const int* incV[G::V] = {}; int incNE = -1; unsigned long long incSum = 0; bool incValid = false;
@@ -236,7 +404,7 @@ struct GraphOps : EnergyOps<T> {
     }
     void bind(void** p, LaunchCtx& ctx) override {
         g.bindParams(p);
-        if (useGather && (long)g.nE * G::V > 0x7fffffffL) useGather = false;      // incidence ids j * nE + e are 32-bit: beyond that, scatter
+        if (useGather && (long)g.nE * G::V > 0x7fffffffL) { useGather = false; gatherTooLarge = true; }      // incidence ids j * nE + e are 32-bit: beyond that, scatter
         if (useGather) ensureIncidence(ctx);
     }
     T* unknownPtr(int img) const override { return const_cast<T*>(g.X[img]); }
@@ -255,7 +423,59 @@ struct GraphOps : EnergyOps<T> {
         { ScopedKernel k(ctx, "PCGInit1"); ge_vertices<T, G, 2><<<vgrid(), kBlock, 0, ctx.stream>>>(g, nullptr, vo, r, diag, nullptr, nullptr); }
         { ScopedKernel k(ctx, "PCGInit1_Graph"); ge_edges<T, G, 2><<<edgeGrid(g.nE, cus), kBlock, 0, ctx.stream>>>(g, nullptr, vo, r, diag, nullptr); }
     }
+    // ---- amd_graph_fused = 1 (EnergyOps::graphFused): J^T J p by ge_gather, the PCG iteration as ge_flatStep + ge_gather ----
+    // THE predicate of the path: nullptr, or why the plan keeps the record kernels.  applyJTJ, pcgIteration and describe() all ask here.
+    const char* fusedWhyNot() const {
+        if (!useGather) return gatherTooLarge ? "more than 2^31 incidences (scatter mode)" : "scatter mode (OPT_AMD_GRAPH_GATHER=0)";
+        return nullptr;
+    }
+    bool fusedOn() const { return this->graphFused && !fusedWhyNot(); }
+    int launchGather(const T* v, T* out, const T* CtC, double* dotPartials, const GeIterSums<T>& S, LaunchCtx& ctx) {
+        const int gv = vgrid(GE_GATHER_LANES);
+        if (CtC) ge_gather<T, G, true><<<gv, kBlock, 0, ctx.stream>>>(g, v, vo, out, CtC, dotPartials, incidence(), S);
+        else ge_gather<T, G, false><<<gv, kBlock, 0, ctx.stream>>>(g, v, vo, out, nullptr, dotPartials, incidence(), S);
+        return gv;
+    }
+    bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
+        const bool lmv = a.CtC != nullptr;
+        if (!fusedOn() || !a.pre || this->slab.active || (lmv && !(a.b && a.q))) return false;
+        const long nPad = (this->nScalars + 3) / 4 * 4;      // the solver's vectors (zero beyond nScalars)
+        const int gf = flatGrid(nPad, cus, kMaxPartials / 2);
+        if (a.first) {      // the solver adopts rNew / pNew after every launch: the start state moves there unchanged
+            HIP_CHECK(hipMemcpyAsync(a.rNew, a.rOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
+            HIP_CHECK(hipMemcpyAsync(a.pNew, a.pOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
+        } else if (lmv) {
+            ScopedKernel k(ctx, "PCGStep2+PCGStep3");
+            const GeLmStep<T> L{a.b, a.deltaOut ? a.deltaOut : a.delta, a.q->partials, a.qTag, a.afterReset, a.betaNum.partials, a.betaNum.n, a.betaDen.partials, a.betaDen.n};
+            ge_flatStep<T, true><<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n, a.aDenPrev.partials, a.aDenPrev.n,
+                                                                a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L);
+            if (!a.afterReset) a.q->n = gf;
+        } else {
+            ScopedKernel k(ctx, "PCGStep2+PCGStep3");
+            ge_flatStep<T, false><<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n, a.aDenPrev.partials, a.aDenPrev.n,
+                                                                 a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, GeLmStep<T>{});
+        }
+        ScopedKernel k(ctx, "PCGStep1");
+        const int gv = launchGather(a.pNew, a.ApNew, a.CtC, a.aDen->partials, GeIterSums<T>{a.rNew, a.pre, a.aNum->partials, a.s2->partials, a.s3->partials}, ctx);
+        a.aNum->n = a.aDen->n = a.s2->n = a.s3->n = gv;
+        return true;
+    }
+    std::string describe(int, bool lmv, const OnChipLm<T>*) override {      // ("key=value; ..." -- no ';' inside a value)
+        if (!this->graphFused) return "path=launch-per-iteration";
+        const char* why = fusedWhyNot();
+        if (!why && !this->usePreconditioner) why = "no preconditioner";
+        char buf[300];
+        if (why) snprintf(buf, sizeof buf, "path=launch-per-iteration; why_not_fused=%s", why);
+        else snprintf(buf, sizeof buf, "path=launch-per-iteration; launches_per_iteration=2; kernels=ge_flatStep+ge_gather<%s, %s, %s>", sizeof(T) == 4 ? "float" : "double", G::kName, lmv ? "LM" : "GN");
+        return buf;
+    }
     void applyJTJ(const T* v, T* out, const T* CtC, Reduction* dot, LaunchCtx& ctx) override {
+        if (fusedOn()) {      // one launch instead of two, the same bits in `out`
+            ScopedKernel k(ctx, "PCGStep1");
+            const int gv = launchGather(v, out, CtC, dot ? dot->partials : nullptr, GeIterSums<T>{nullptr, nullptr, nullptr, nullptr, nullptr}, ctx);
+            if (dot) dot->n = gv;
+            return;
+        }
         const int gv = vgrid(useGather ? GE_GATHER_LANES : 1), ge = edgeGrid(g.nE, cus);
         if (useGather) {
             { ScopedKernel k(ctx, "PCGStep1_Graph"); ge_edges<T, G, 3><<<ge, kBlock, 0, ctx.stream>>>(g, v, vo, out, nullptr, dot ? dot->partials + gv : nullptr, rec); }

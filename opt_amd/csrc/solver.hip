@@ -1000,7 +1000,7 @@ struct PcgSolver : SolverBase {
         onChipFailure("the solve goes back to that step");
         sp.nIter = f;
     }
-    void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipPre = preconditioner; }      // (EnergyOps::onChipLevel)
+    void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipPre = preconditioner; E->graphFused = sp.amd_graph_fused != 0 && sp.amd_reference_order == 0; }      // (EnergyOps::onChipLevel, graphFused)
     int stepOnce(void** params, bool& again) {
         tellOnChipLevel();
         if (!(insideSolve && boundForSolve && E->bindInvariantDuringSolve())) E->bind(params, ctx);      // (EnergyOps::bindInvariantDuringSolve: once per Opt_ProblemSolve where nothing bind() derives can have changed)
@@ -1294,6 +1294,7 @@ struct PcgSolver : SolverBase {
         HIP_CHECK(hipMemcpy(diag, Ap_X, n * sizeof(T), hipMemcpyDeviceToDevice));
     }
     double applyJTJ(void** params, const void* v, void* out) override {
+        tellOnChipLevel();      // (amd_graph_fused decides which kernels a functor mesh energy applies J^T J with)
         E->bind(params, ctx); exchangeUnknowns(); E->precompute(ctx);
         E->evalJTF(z, CtC, ctx);   // refreshes the energy's per-iteration auxiliaries (e.g. cos/sin tables)
         HIP_CHECK(hipMemsetAsync(p, 0, nPad * sizeof(T), stream));
@@ -1340,7 +1341,7 @@ bool SolverBase::setParameter(const char* name, const void* value) {   // solver
     PF(min_relative_decrease) PF(min_trust_region_radius) PF(max_trust_region_radius) PF(q_tolerance) PF(function_tolerance)
     PF(trust_region_radius) PF(radius_decrease_factor) PF(min_lm_diagonal) PF(max_lm_diagonal)
     PI(residual_reset_period) PI(nIter) PI(nIterations) PI(lIterations) PI(patchIterations) PI(patchSize)
-    PI(amd_reference_order) PI(amd_onchip)
+    PI(amd_reference_order) PI(amd_onchip) PI(amd_graph_fused)
 #undef PF
 #undef PI
     return false;

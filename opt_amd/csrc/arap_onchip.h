@@ -10,16 +10,21 @@
 //   r, A p (and M where the registers allow) of a lane's V vertices in registers; vertex s * blockDim + tid is slot s of thread tid, so the ELL lists, the static
 //           planes T0 / T1 / U0 of this Gauss-Newton step (arap_buildStatic) and the solver's vectors are read coalesced; b, CtC (LM) and the static planes are re-read
 //           from memory where they are used: a few kilobytes that stay in the CU's cache;
-//   A p     the gather of arap_applyEll over the same planes and ELL out-lists, the same expressions in the same order per vertex (the text below is that kernel's: it is
-//           repeated, not shared, so that the streaming kernels keep their code and their bits);
+//   A p     the gather of arap_applyEll over the same planes and ELL out-lists, the same expressions in the same order per vertex: both kernels include
+//           arap_half_edge_pair.inc for the walk's body, and differ only in where a neighbour's p comes from;
 //   sums    formed in double; wave sum (ocWaveSum63), one partial per wave in LDS, every lane adds the partials in wave order: the same bits in every lane, in every run.
-// The iterates are those of the two-kernel loop -- alpha from sum p . A p, beta's numerator by the expansion aNum - 2 alpha s2 + alpha^2 s3 clamped at 0, the reference's
-// guards -- only the order of the sums differs, which is why the path is opt-in.  Levenberg-Marquardt: A = J^T J + diag(CtC), b = r_0, Q = 1/2 sum delta . (r + b) carried
+// The iterates are those of the two-kernel loop -- its terms of the sums (graph_pcg.h iterTerm), its alpha and beta (ocAlpha, ocBeta: the values of
+// graph_flat_scalars.inc) -- only the order of the sums differs, which is why the path is opt-in.  Two pieces remain COPIES of the streaming kernels' text, not shared
+// with them: the centred part at the end of aoApply (arap_applyEll's, arap_applyFused's) and the per-scalar update of the step (arap_flatStepPlanes'); as functions they
+// changed the streaming kernels' instructions (profiles/graph_shared_text.md).  A change to either has to be made in every copy;
+// tests/test_onchip_arap_gpu.py::test_same_iterates_as_the_two_kernel_loop is what notices a copy that drifts.
+// Levenberg-Marquardt: A = J^T J + diag(CtC), b = r_0, Q = 1/2 sum delta . (r + b) carried
 // by the next iteration's sums, the q early-out (onchip_sync.h ocZetaBreak), and the split residual reset (solverGPUGaussNewton.t:1077-1086) as a second gather pass A delta
 // at every residual_reset_period-th iteration -- inside one workgroup that costs a barrier.
 // Synchronisation: __syncthreads and nothing else.  No polling loop, no tagged word, no co-residency requirement, no time-out path; every break is decided from totals
 // that are the same bits in every lane, so every barrier is reached by every wave.
 #pragma once
+#include "graph_pcg.h"
 #include "onchip_sync.h"
 
 namespace optamd {
@@ -61,28 +66,7 @@ __device__ __forceinline__ void aoApply(const ArapOcArgs<T>& K, const Q4<T>* __r
         for (int j = 0; j < BATCH; ++j) { nd0[j] = L0[nid[j]]; nd1[j] = L1[nid[j]]; nt0[j] = P.T0[nid[j]]; nt1[j] = P.T1[nid[j]]; nu0[j] = P.U0[nid[j]]; }
 #pragma unroll
         for (int j = 0; j < BATCH; ++j) {
-            const T wj = wm[j];
-            const V3<T> np{nd0[j].a, nd0[j].b, nd0[j].c}, npa{nd0[j].d, nd1[j].a, nd1[j].b};
-            const V3<T> u{u0.a - nu0[j].a, u0.b - nu0[j].b, u0.c - nu0[j].c}, un{-u.x, -u.y, -u.z};
-            V3<T> D0, D1, D2;
-            arap_cols(cv, u, D0, D1, D2);
-            {   // out-edge (v -> u): J p and D_k . J p
-                const T jx = w * (pv.x - np.x) - w * (D0.x * pav.x + D1.x * pav.y + D2.x * pav.z);
-                const T jy = w * (pv.y - np.y) - w * (D0.y * pav.x + D1.y * pav.y + D2.y * pav.z);
-                const T jz = w * (pv.z - np.z) - w * (D0.z * pav.x + D1.z * pav.y + D2.z * pav.z);
-                s0 += wj * jx; s1 += wj * jy; s2 += wj * jz;
-                s3 -= wj * (D0.x * jx + D0.y * jy + D0.z * jz); s4 -= wj * (D1.x * jx + D1.y * jy + D1.z * jz); s5 -= wj * (D2.x * jx + D2.y * jy + D2.z * jz);
-                if (wj != T(0)) acc += (double)(jx * jx + jy * jy + jz * jz);
-            }
-            {   // its reverse (u -> v): only its J p reaches this vertex's Offset row
-                const ArapCoef<T> cu = arap_coef(nt0[j].a, nt0[j].b, nt0[j].c, nt0[j].d, nt1[j].a, nt1[j].b);
-                V3<T> E0, E1, E2;
-                arap_cols(cu, un, E0, E1, E2);
-                const T jx = w * (np.x - pv.x) - w * (E0.x * npa.x + E1.x * npa.y + E2.x * npa.z);
-                const T jy = w * (np.y - pv.y) - w * (E0.y * npa.x + E1.y * npa.y + E2.y * npa.z);
-                const T jz = w * (np.z - pv.z) - w * (E0.z * npa.x + E1.z * npa.y + E2.z * npa.z);
-                s0 -= wj * jx; s1 -= wj * jy; s2 -= wj * jz;
-            }
+#include "arap_half_edge_pair.inc"
         }
     }
     // per-vertex ("centred") part: fitting term and, for LM, CtC p
@@ -180,9 +164,9 @@ __global__ __launch_bounds__(kAoMaxBlock) void arap_onchipPcg(ArapOcArgs<T> K) {
             if (ok[s]) {
                 V3<T> mo, ma; loadM(s, mo, ma);
                 const V3<T>&ro = rO[s], &ra = rA[s], &oO = aO[s], &oA = aA[s];
-                sums[0] += arap_dprod3(mo.x, ro.x, ro.x) + arap_dprod3(mo.y, ro.y, ro.y) + arap_dprod3(mo.z, ro.z, ro.z) + arap_dprod3(ma.x, ra.x, ra.x) + arap_dprod3(ma.y, ra.y, ra.y) + arap_dprod3(ma.z, ra.z, ra.z);
-                sums[2] += arap_dprod3(mo.x, ro.x, oO.x) + arap_dprod3(mo.y, ro.y, oO.y) + arap_dprod3(mo.z, ro.z, oO.z) + arap_dprod3(ma.x, ra.x, oA.x) + arap_dprod3(ma.y, ra.y, oA.y) + arap_dprod3(ma.z, ra.z, oA.z);
-                sums[3] += arap_dprod3(mo.x, oO.x, oO.x) + arap_dprod3(mo.y, oO.y, oO.y) + arap_dprod3(mo.z, oO.z, oO.z) + arap_dprod3(ma.x, oA.x, oA.x) + arap_dprod3(ma.y, oA.y, oA.y) + arap_dprod3(ma.z, oA.z, oA.z);
+                sums[0] += iterTerm(mo.x, ro.x, ro.x) + iterTerm(mo.y, ro.y, ro.y) + iterTerm(mo.z, ro.z, ro.z) + iterTerm(ma.x, ra.x, ra.x) + iterTerm(ma.y, ra.y, ra.y) + iterTerm(ma.z, ra.z, ra.z);
+                sums[2] += iterTerm(mo.x, ro.x, oO.x) + iterTerm(mo.y, ro.y, oO.y) + iterTerm(mo.z, ro.z, oO.z) + iterTerm(ma.x, ra.x, oA.x) + iterTerm(ma.y, ra.y, oA.y) + iterTerm(ma.z, ra.z, oA.z);
+                sums[3] += iterTerm(mo.x, oO.x, oO.x) + iterTerm(mo.y, oO.y, oO.y) + iterTerm(mo.z, oO.z, oO.z) + iterTerm(ma.x, oA.x, oA.x) + iterTerm(ma.y, oA.y, oA.y) + iterTerm(ma.z, oA.z, oA.z);
             }
         }
         if constexpr (LMV) sums[NS - 1] = accQ;

@@ -19,7 +19,7 @@
 // that target the same head vertex folded by a segmented shuffle reduction into one hardware f32 / f64 atomic) is what cost, model cost and curveFitting still use,
 // and the J^T J p alternative of development builds (-DOPT_AMD_DEV_SWITCHES, OPT_AMD_ARAP_GATHER=0).
 #include "energy.h"
-#include "graph_common.h"
+#include "graph_pcg.h"
 #include <hipcub/hipcub.hpp>
 #include <cstring>
 
@@ -128,9 +128,7 @@ struct ArapArgs {
     T* D;   // per-edge dR3/da_k (U_v0 - U_v1), k = 0..2: 9 planes of nE scalars, rebuilt by the PCGInit1_Graph pass of every
             // Gauss-Newton iteration so that the PCG loop's edge kernel needs no sin/cos (3 sincos per edge per iteration otherwise)
 };
-template <class T> struct V3 { T x, y, z; };
 template <class T> __device__ __forceinline__ V3<T> ld3(const T* p, long i) { return V3<T>{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-template <class T> __device__ __forceinline__ T dot3(const V3<T>& a, const V3<T>& b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
 // rotated edge R3(a) u and the three derivative columns D_k = dR3/da_k u   (Rotate3D, reference lib.t:77-91)
 template <class T>
@@ -311,17 +309,11 @@ template <class T>
 __global__ __launch_bounds__(kBlock) void arap_packD(const T* __restrict__ D, T* __restrict__ D9, long nE) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < 9 * nE; i += (long)gridDim.x * blockDim.x) D9[i] = D[(i % 9) * nE + i / 9];
 }
-// S.r != nullptr (round 3): the launch is the Step1 half of a TWO-kernel PCG iteration (arap_flatStepPlanes + arap_applyEll; EnergyOps::pcgIteration).  Besides p . A p it then sums, at the
-// lane that owns the vertex, what the expanded beta numerator of the next flat pass needs -- sum M r^2, sum M r . A p, sum M (A p)^2, every term from M, r, A p themselves in double
-// (exact products of floats; see energy_image_warping.hip dprod3) -- so that PCGStep2 and PCGStep3 become one flat pass without a reduction between them.
-template <class T> __device__ __forceinline__ double arap_dprod3(T m, T a, T b) { return ((double)m * (double)a) * (double)b; }
-struct ArapIterSums { const void* r; const void* M; double *aNum, *s2, *s3; };
 template <class T>
 __global__ __launch_bounds__(kBlock) void arap_applyFused(ArapArgs<T> A, GraphCsr G, const T* __restrict__ D9, const T* __restrict__ v, T* __restrict__ out,
-                                                          const T* __restrict__ CtC, double* __restrict__ partials, ArapIterSums S = ArapIterSums{nullptr, nullptr, nullptr, nullptr, nullptr}) {
-    __shared__ double scratch[4 * (kBlock / kWave + 1)];
-    double acc = 0, accNum = 0, acc2 = 0, acc3 = 0;
-    const T* rv = (const T*)S.r; const T* Mv = (const T*)S.M;
+                                                          const T* __restrict__ CtC, double* __restrict__ partials) {
+    __shared__ double scratch[kBlock / kWave + 1];
+    double acc = 0;
     const long offA = 3 * A.N;
     const int sub = threadIdx.x % kLanesPerVertex, slot = sub;
     const long nGroups = (A.N + (kBlock / kLanesPerVertex) - 1) / (kBlock / kLanesPerVertex);
@@ -331,8 +323,6 @@ __global__ __launch_bounds__(kBlock) void arap_applyFused(ArapArgs<T> A, GraphCs
         const long iv = ok ? i : 0;
         const T w = A.w_reg;
         const V3<T> pv = ld3(v, iv), pav = ld3(v + offA, iv);
-        V3<T> rO{0, 0, 0}, rA{0, 0, 0}, mO{0, 0, 0}, mA{0, 0, 0};
-        if (rv) { rO = ld3(rv, iv); rA = ld3(rv + offA, iv); mO = ld3(Mv, iv); mA = ld3(Mv + offA, iv); }      // requested before the edge walk: known from the vertex index alone
         T s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
         const int bo = G.outOff[iv], eo = ok ? G.outOff[iv + 1] : bo, bi = G.inOff[iv], ei = ok ? G.inOff[iv + 1] : bi;
         for (int k = 0; k < max(eo - bo, ei - bi); k += kLanesPerVertex) {
@@ -372,35 +362,12 @@ __global__ __launch_bounds__(kBlock) void arap_applyFused(ArapArgs<T> A, GraphCs
             const V3<T> oO{q.x + s0, q.y + s1, q.z + s2}, oA{qa.x + s3, qa.y + s4, qa.z + s5};
             out[3 * i] = oO.x; out[3 * i + 1] = oO.y; out[3 * i + 2] = oO.z;
             out[offA + 3 * i] = oA.x; out[offA + 3 * i + 1] = oA.y; out[offA + 3 * i + 2] = oA.z;
-            if (rv) {
-                accNum += arap_dprod3(mO.x, rO.x, rO.x) + arap_dprod3(mO.y, rO.y, rO.y) + arap_dprod3(mO.z, rO.z, rO.z) + arap_dprod3(mA.x, rA.x, rA.x) + arap_dprod3(mA.y, rA.y, rA.y) + arap_dprod3(mA.z, rA.z, rA.z);
-                acc2 += arap_dprod3(mO.x, rO.x, oO.x) + arap_dprod3(mO.y, rO.y, oO.y) + arap_dprod3(mO.z, rO.z, oO.z) + arap_dprod3(mA.x, rA.x, oA.x) + arap_dprod3(mA.y, rA.y, oA.y) + arap_dprod3(mA.z, rA.z, oA.z);
-                acc3 += arap_dprod3(mO.x, oO.x, oO.x) + arap_dprod3(mO.y, oO.y, oO.y) + arap_dprod3(mO.z, oO.z, oO.z) + arap_dprod3(mA.x, oA.x, oA.x) + arap_dprod3(mA.y, oA.y, oA.y) + arap_dprod3(mA.z, oA.z, oA.z);
-            }
         }
-    }
-    if (rv) {
-        double vv[4] = {acc, accNum, acc2, acc3};
-        blockReduceSumN<4>(vv, scratch);
-        if (threadIdx.x == 0) { if (partials) partials[blockIdx.x] = vv[0]; S.aNum[blockIdx.x] = vv[1]; S.s2[blockIdx.x] = vv[2]; S.s3[blockIdx.x] = vv[3]; }
-        return;
     }
     double t = blockReduceSum(acc, scratch);
     if (threadIdx.x == 0 && partials) partials[blockIdx.x] = t;
 }
 
-// PCGStep2 + PCGStep3 of iteration k-1 as ONE flat pass (solver.t:446-489, 537-550): alpha from the previous gather's sums, beta from their expansion
-//   sum M (r - alpha A p)^2 = aNum - 2 alpha s2 + alpha^2 s3   (all in double, clamped at 0 like the direct sum it replaces; energy.h PcgIterArgs),
-// then delta += alpha p, r -= alpha A p, z = M r, p = z + beta p -- no reduction in this kernel, none between Step2 and Step3.
-// ---- round 3: J^T J p on a SYMMETRIC graph from one record per vertex ---------------------------------------------------------------------------
-// arap_applyFused is bound by the number of dependent index -> record chains in flight: per half-edge slot it follows outIdx / inIdx / outNbr / inNbr (16 B), two 36-byte
-// derivative rows and three 12-byte vectors of the neighbour, 3-5 cache lines.  A mesh carries every edge in both directions (examples/shared/OptGraph.h builds v0 -> v1 for
-// every neighbour of every vertex), so the in-edges of v are the reversed out-edges of v: (u -> v) exists exactly as often as (v -> u) -- checked per vertex when the edge
-// lists are built (csr_symmetric), any other graph keeps arap_applyFused.  Then one walk of the out-list serves both directions, and everything the walk needs from a
-// neighbour u -- p_u, pa_u and the sines / cosines of its angles, from which its derivative columns D_k(u -> v) = dR3/da_k(a_u) (U_u - U_v) follow in ~60 flops instead of a
-// 36-byte row -- is ONE 64-byte record (one cache line); the slot itself is 16 contiguous bytes {U_v - U_u, u}.  Per half-edge pair: 80 B in two lines instead of ~190 B in
-// seven.  The expressions are arap_edges<3>'s / arap_rot's (same association: J p = w (p_v0 - p_v1) - w (D_0 pa.x + D_1 pa.y + D_2 pa.z)), the in-edge terms are summed in
-// out-list order.
 // ---- symmetric-graph path, round 6 layout: 16-byte SoA PLANES + ELL out-lists, one lane per vertex ---------------------------------------------------------
 // What a half-edge's arithmetic needs of its neighbour u -- p_u, the Angle part of p_u, the sines / cosines of u's angles, u's rest position -- used to be one 64-byte
 // record per vertex, gathered with 16-byte loads: every lane of a gather touched a cache line of its own, four times over, and the vector L1's line rate (one line per clock
@@ -412,31 +379,7 @@ __global__ __launch_bounds__(kBlock) void arap_applyFused(ArapArgs<T> A, GraphCs
 // and the out-lists are stored ELL-wise: ell[j * N + v] = the j-th out-neighbour of v (v itself beyond its degree, weight 0), so slot j of consecutive vertices is contiguous.
 // A vertex with more than kEllMax neighbours sends the graph to the edge-list gather (arap_applyFused), like an asymmetric one.
 constexpr int kEllMax = 16;
-template <class T> struct alignas(16) Q4 { T a, b, c, d; };
 template <class T> struct ArapPlanes { Q4<T>* D0; Q4<T>* D1; Q4<T>* T0; Q4<T>* T1; Q4<T>* U0; const int* ell; const int* deg; int K; };
-template <class T> struct ArapCoef { T a0, a1, a2, a3, a4, a5, b0, b1, b2, b3, b4, b5, b6, b7, b8, c0, c1, c2, c3, c4, c5; };
-// the non-zero entries of dR3/d alpha, d beta, d gamma (arap_rot's coefficients, same products)
-template <class T>
-__device__ __forceinline__ ArapCoef<T> arap_coef(T sa, T ca, T sb, T cb, T sg, T cg) {
-    ArapCoef<T> c;
-    c.a0 = sg * sa + cg * sb * ca;  c.a1 = sg * ca - cg * sb * sa;
-    c.a2 = -cg * sa + sg * sb * ca; c.a3 = -cg * ca - sg * sb * sa;
-    c.a4 = cb * ca;                 c.a5 = -cb * sa;
-    c.b0 = -cg * sb; c.b1 = cg * cb * sa; c.b2 = cg * cb * ca;
-    c.b3 = -sg * sb; c.b4 = sg * cb * sa; c.b5 = sg * cb * ca;
-    c.b6 = -cb;      c.b7 = -sb * sa;     c.b8 = -sb * ca;
-    c.c0 = -sg * cb; c.c1 = -cg * ca - sg * sb * sa; c.c2 = cg * sa - sg * sb * ca;
-    c.c3 = cg * cb;  c.c4 = -sg * ca + cg * sb * sa; c.c5 = sg * sa + cg * sb * ca;
-    return c;
-}
-template <class T>
-__device__ __forceinline__ void arap_cols(const ArapCoef<T>& c, const V3<T>& u, V3<T>& D0, V3<T>& D1, V3<T>& D2) {
-    D0.x = c.a0 * u.y + c.a1 * u.z; D0.y = c.a2 * u.y + c.a3 * u.z; D0.z = c.a4 * u.y + c.a5 * u.z;
-    D1.x = c.b0 * u.x + c.b1 * u.y + c.b2 * u.z; D1.y = c.b3 * u.x + c.b4 * u.y + c.b5 * u.z; D1.z = c.b6 * u.x + c.b7 * u.y + c.b8 * u.z;
-    D2.x = c.c0 * u.x + c.c1 * u.y + c.c2 * u.z; D2.y = c.c3 * u.x + c.c4 * u.y + c.c5 * u.z; D2.z = 0;
-}
-template <class T> __device__ __forceinline__ V3<T> ldv3(const T* p, long i) { return reinterpret_cast<const V3<T>*>(p)[i]; }      // one 12 / 24-byte load
-template <class T> __device__ __forceinline__ void stv3(T* p, long i, const V3<T>& v) { reinterpret_cast<V3<T>*>(p)[i] = v; }
 // per vertex: is the multiset of out-neighbours the multiset of in-neighbours?  (quadratic in the degree; lists longer than 64 are declared asymmetric)
 __global__ __launch_bounds__(kBlock) void csr_symmetric(long N, const int* __restrict__ outOff, const int* __restrict__ outNbr, const int* __restrict__ inOff, const int* __restrict__ inNbr,
                                                         int* __restrict__ notSym) {
@@ -526,10 +469,9 @@ struct XcdWalk {
 #endif
 template <class T, int BATCH>
 __global__ __launch_bounds__(kBlock) void arap_applyEll(ArapArgs<T> A, ArapPlanes<T> P, const T* __restrict__ v, T* __restrict__ out, const T* __restrict__ CtC, double* __restrict__ partials,
-                                                        int xcd, ArapIterSums S) {
+                                                        int xcd, IterSums<T> S) {
     __shared__ double scratch[4 * (kBlock / kWave + 1)];
-    double acc = 0, accNum = 0, acc2 = 0, acc3 = 0;      // S.r != nullptr: the Step1 half of a two-kernel PCG iteration, see arap_applyFused
-    const T* rv = (const T*)S.r; const T* Mv = (const T*)S.M;
+    double acc = 0, accNum = 0, acc2 = 0, acc3 = 0;      // S.r != nullptr: the Step1 half of a two-kernel PCG iteration (arap_flatStepPlanes + arap_applyEll), see graph_pcg.h IterSums
     const long N = A.N, offA = 3 * N;
     const XcdWalk walk((N + kBlock - 1) / kBlock, xcd);
     const T w = A.w_reg;
@@ -544,7 +486,7 @@ __global__ __launch_bounds__(kBlock) void arap_applyEll(ArapArgs<T> A, ArapPlane
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) dmax = max(dmax, __shfl_xor(dmax, o, kWave));      // the wave walks as many slots as its longest list
         V3<T> rO{0, 0, 0}, rA{0, 0, 0}, mO{0, 0, 0}, mA{0, 0, 0};
-        if (rv) { rO = ldv3(rv, iv); rA = ldv3(rv + offA, iv); mO = ldv3(Mv, iv); mA = ldv3(Mv + offA, iv); }      // requested before the walk: known from the vertex index alone
+        if (S.r) { rO = ldv3(S.r, iv); rA = ldv3(S.r + offA, iv); mO = ldv3(S.M, iv); mA = ldv3(S.M + offA, iv); }      // requested before the walk: known from the vertex index alone
         const V3<T> pv{d0.a, d0.b, d0.c}, pav{d0.d, d1.a, d1.b};
         const ArapCoef<T> cv = arap_coef(t0.a, t0.b, t0.c, t0.d, t1.a, t1.b);
         T s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
@@ -557,28 +499,7 @@ __global__ __launch_bounds__(kBlock) void arap_applyEll(ArapArgs<T> A, ArapPlane
             for (int j = 0; j < BATCH; ++j) { nd0[j] = P.D0[nid[j]]; nd1[j] = P.D1[nid[j]]; nt0[j] = P.T0[nid[j]]; nt1[j] = P.T1[nid[j]]; nu0[j] = P.U0[nid[j]]; }
 #pragma unroll
             for (int j = 0; j < BATCH; ++j) {
-                const T wj = wm[j];
-                const V3<T> np{nd0[j].a, nd0[j].b, nd0[j].c}, npa{nd0[j].d, nd1[j].a, nd1[j].b};
-                const V3<T> u{u0.a - nu0[j].a, u0.b - nu0[j].b, u0.c - nu0[j].c}, un{-u.x, -u.y, -u.z};      // U_v - U_u: the subtraction the slots of rounds 3-5 stored
-                V3<T> D0, D1, D2;
-                arap_cols(cv, u, D0, D1, D2);
-                {   // out-edge (v -> u): J p and D_k . J p  (arap_edges<3> with v0 = v)
-                    const T jx = w * (pv.x - np.x) - w * (D0.x * pav.x + D1.x * pav.y + D2.x * pav.z);
-                    const T jy = w * (pv.y - np.y) - w * (D0.y * pav.x + D1.y * pav.y + D2.y * pav.z);
-                    const T jz = w * (pv.z - np.z) - w * (D0.z * pav.x + D1.z * pav.y + D2.z * pav.z);
-                    s0 += wj * jx; s1 += wj * jy; s2 += wj * jz;
-                    s3 -= wj * (D0.x * jx + D0.y * jy + D0.z * jz); s4 -= wj * (D1.x * jx + D1.y * jy + D1.z * jz); s5 -= wj * (D2.x * jx + D2.y * jy + D2.z * jz);
-                    if (wj != T(0)) acc += (double)(jx * jx + jy * jy + jz * jz);              // sum_u p_u (J^T J p)_u of this edge = |J p|^2 (o.t:2117-2122)
-                }
-                {   // its reverse (u -> v): only its J p reaches this vertex's Offset row
-                    const ArapCoef<T> cu = arap_coef(nt0[j].a, nt0[j].b, nt0[j].c, nt0[j].d, nt1[j].a, nt1[j].b);
-                    V3<T> E0, E1, E2;
-                    arap_cols(cu, un, E0, E1, E2);
-                    const T jx = w * (np.x - pv.x) - w * (E0.x * npa.x + E1.x * npa.y + E2.x * npa.z);
-                    const T jy = w * (np.y - pv.y) - w * (E0.y * npa.x + E1.y * npa.y + E2.y * npa.z);
-                    const T jz = w * (np.z - pv.z) - w * (E0.z * npa.x + E1.z * npa.y + E2.z * npa.z);
-                    s0 -= wj * jx; s1 -= wj * jy; s2 -= wj * jz;
-                }
+#include "arap_half_edge_pair.inc"
             }
         }
         if (ok) {
@@ -590,19 +511,14 @@ __global__ __launch_bounds__(kBlock) void arap_applyEll(ArapArgs<T> A, ArapPlane
             acc += (double)(dot3(pv, q) + dot3(pav, qa));
             const V3<T> oO{q.x + s0, q.y + s1, q.z + s2}, oA{qa.x + s3, qa.y + s4, qa.z + s5};
             stv3(out, i, oO); stv3(out + offA, i, oA);
-            if (rv) {
-                accNum += arap_dprod3(mO.x, rO.x, rO.x) + arap_dprod3(mO.y, rO.y, rO.y) + arap_dprod3(mO.z, rO.z, rO.z) + arap_dprod3(mA.x, rA.x, rA.x) + arap_dprod3(mA.y, rA.y, rA.y) + arap_dprod3(mA.z, rA.z, rA.z);
-                acc2 += arap_dprod3(mO.x, rO.x, oO.x) + arap_dprod3(mO.y, rO.y, oO.y) + arap_dprod3(mO.z, rO.z, oO.z) + arap_dprod3(mA.x, rA.x, oA.x) + arap_dprod3(mA.y, rA.y, oA.y) + arap_dprod3(mA.z, rA.z, oA.z);
-                acc3 += arap_dprod3(mO.x, oO.x, oO.x) + arap_dprod3(mO.y, oO.y, oO.y) + arap_dprod3(mO.z, oO.z, oO.z) + arap_dprod3(mA.x, oA.x, oA.x) + arap_dprod3(mA.y, oA.y, oA.y) + arap_dprod3(mA.z, oA.z, oA.z);
+            if (S.r) {
+                accNum += iterTerm(mO.x, rO.x, rO.x) + iterTerm(mO.y, rO.y, rO.y) + iterTerm(mO.z, rO.z, rO.z) + iterTerm(mA.x, rA.x, rA.x) + iterTerm(mA.y, rA.y, rA.y) + iterTerm(mA.z, rA.z, rA.z);
+                acc2 += iterTerm(mO.x, rO.x, oO.x) + iterTerm(mO.y, rO.y, oO.y) + iterTerm(mO.z, rO.z, oO.z) + iterTerm(mA.x, rA.x, oA.x) + iterTerm(mA.y, rA.y, oA.y) + iterTerm(mA.z, rA.z, oA.z);
+                acc3 += iterTerm(mO.x, oO.x, oO.x) + iterTerm(mO.y, oO.y, oO.y) + iterTerm(mO.z, oO.z, oO.z) + iterTerm(mA.x, oA.x, oA.x) + iterTerm(mA.y, oA.y, oA.y) + iterTerm(mA.z, oA.z, oA.z);
             }
         }
     }
-    if (rv) {
-        double vv[4] = {acc, accNum, acc2, acc3};
-        blockReduceSumN<4>(vv, scratch);
-        if (threadIdx.x == 0) { if (partials) partials[blockIdx.x] = vv[0]; S.aNum[blockIdx.x] = vv[1]; S.s2[blockIdx.x] = vv[2]; S.s3[blockIdx.x] = vv[3]; }
-        return;
-    }
+    if (S.r) { double vv[4] = {acc, accNum, acc2, acc3}; storeIterSums(vv, partials, S, scratch); return; }
     double t = blockReduceSum(acc, scratch);
     if (threadIdx.x == 0 && partials) partials[blockIdx.x] = t;
 }
@@ -610,31 +526,14 @@ __global__ __launch_bounds__(kBlock) void arap_applyEll(ArapArgs<T> A, ArapPlane
 // PCGStep2 + PCGStep3 in one flat pass for the plane path, one thread per vertex: 12-byte (24-byte) loads of the vertex's Offset and Angle parts of delta, p, r, A p, M, the
 // updates, and the vertex's dynamic planes in two coalesced 16-byte stores (rounds 3-5 moved 16-byte packs and passed the new p through LDS to a thread that wrote 24 B
 // of a 64 B record with six dword stores -- 41 % of the launch stalled on issue).
-// LM (Levenberg-Marquardt, round 6): the same pass with the reference's LM extras -- delta goes to deltaOut (the solver enqueues the next launch before it has read Q:
-// an early-out must still find the old delta), Q_{k-1} = 1/2 sum delta . (r + b) (solver.t:483-485) leaves as per-workgroup partials (tagged words if qTag != 0), and
-// after a split residual reset (L.afterReset: delta and r are already the new ones, solver.t:1077-1083) the pass only forms p = M r + beta p with beta = sum bNum / sum bDen.
-struct ArapLmStep { const void* b; void* deltaOut; double* q; unsigned qTag; int afterReset; const double* bNumP; int nbNum; const double* bDenP; int nbDen; };
+// The scalars (graph_flat_scalars.inc) and LM's extras (graph_pcg.h LmStep) are shared with ge_flatStep; after a split residual reset the pass only forms p = M r + beta p.
 template <class T, bool LM>
 __global__ __launch_bounds__(kBlock) void arap_flatStepPlanes(ArapPlanes<T> P, long N, T* __restrict__ delta, const T* __restrict__ pOld, const T* __restrict__ rOld, const T* __restrict__ Ap,
                                                               const T* __restrict__ M, T* __restrict__ rNew, T* __restrict__ pNew,
-                                                              const double* aNumP, int nNum, const double* aDenP, int nDen, const double* s2P, int n2, const double* s3P, int n3, ArapLmStep L, int xcd, int backward) {
+                                                              const double* aNumP, int nNum, const double* aDenP, int nDen, const double* s2P, int n2, const double* s3P, int n3, LmStep<T> L, int xcd, int backward) {
     __shared__ double scratch[4 * (kBlock / kWave + 1)];
-    T alpha, beta;
-    const bool restart = LM && L.afterReset;
-    if (restart) {
-        const double* const ps[2] = {L.bNumP, L.bDenP}; const int ns[2] = {L.nbNum, L.nbDen}; double o2[2];
-        sumPartialsN<2>(ps, ns, scratch, o2);
-        const T bNum = (T)o2[0], bDen = (T)o2[1];
-        alpha = T(0); beta = (bDen > T(0)) ? bNum / bDen : T(0);                            // PCGStep3's guard (solver.t:544-547)
-    } else {
-        const double* const ps[4] = {aNumP, aDenP, s2P, s3P}; const int ns[4] = {nNum, nDen, n2, n3}; double o4[4];
-        sumPartialsN<4>(ps, ns, scratch, o4);
-        const T aNum = (T)o4[0], aDen = (T)o4[1];
-        alpha = (aDen > T(0)) ? aNum / aDen : T(0);                                          // solver.t:456-459
-        const double bNumD = fmax(o4[0] - 2.0 * (double)alpha * o4[2] + (double)alpha * (double)alpha * o4[3], 0.0);
-        beta = (aNum > T(0)) ? (T)bNumD / aNum : T(0);                                       // solver.t:544-547
-    }
-    const T* const bV = (const T*)L.b; T* const dOut = LM ? (T*)L.deltaOut : delta;
+#include "graph_flat_scalars.inc"      // alpha, beta, restart
+    T* const dOut = LM ? L.deltaOut : delta;
     double accQ = 0;
     const long offA = 3 * N;
     const XcdWalk walk((N + kBlock - 1) / kBlock, xcd);
@@ -656,7 +555,7 @@ __global__ __launch_bounds__(kBlock) void arap_flatStepPlanes(ArapPlanes<T> P, l
                 rn = V3<T>{r.x - alpha * a.x, r.y - alpha * a.y, r.z - alpha * a.z};
                 const V3<T> z{m.x * rn.x, m.y * rn.y, m.z * rn.z};
                 pn[h] = V3<T>{z.x + beta * p.x, z.y + beta * p.y, z.z + beta * p.z};
-                if (LM) { const V3<T> bb = ldv3(bV + o, i); accQ += (double)(T(0.5) * (d.x * (rn.x + bb.x))) + (double)(T(0.5) * (d.y * (rn.y + bb.y))) + (double)(T(0.5) * (d.z * (rn.z + bb.z))); }
+                if (LM) { const V3<T> bb = ldv3(L.b + o, i); accQ += (double)(T(0.5) * (d.x * (rn.x + bb.x))) + (double)(T(0.5) * (d.y * (rn.y + bb.y))) + (double)(T(0.5) * (d.z * (rn.z + bb.z))); }
                 stv3(dOut + o, i, d);
             }
             stv3(rNew + o, i, rn); stv3(pNew + o, i, pn[h]);
@@ -906,7 +805,7 @@ struct ArapOps : EnergyOps<T> {
     int symGridCap = 0;                 // OPT_AMD_ARAP_VGRID (read per plan)
     int flatBackward = 1;               // OPT_AMD_ARAP_WALK=0: the flat pass walks its eighths forward like the gather (A/B switch, see XcdWalk)
     int symXcd = 1;                     // OPT_AMD_ARAP_SYM_XCD=0: consecutive vertex groups on consecutive workgroups (A/B switch, see arap_applyEll)
-    int launchSym(const T* v, T* out, const T* CtC, Reduction* dot, LaunchCtx& ctx, const ArapIterSums& S = ArapIterSums{nullptr, nullptr, nullptr, nullptr, nullptr}) {
+    int launchSym(const T* v, T* out, const T* CtC, Reduction* dot, LaunchCtx& ctx, const IterSums<T>& S = IterSums<T>{nullptr, nullptr, nullptr, nullptr, nullptr}) {
         const int g = symGrid();
         double* part = dot ? dot->partials : nullptr;
         arap_applyEll<T, ARAP_ELL_BATCH><<<g, kBlock, 0, ctx.stream>>>(A, planes, v, out, CtC, part, symXcd && g % 8 == 0, S);
@@ -926,33 +825,20 @@ struct ArapOps : EnergyOps<T> {
     // kernels per iteration.)  On the edge-list gather of asymmetric graphs the same fusion lost in three formulations (profiles/NOTES.md) and is not offered.
     int fusedIterEnv = -1;
     bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
-        // Gauss-Newton and (round 6) Levenberg-Marquardt: a.CtC adds CtC p to the gather, the flat pass carries b, Q and the restart after a residual reset (ArapLmStep)
-        const bool lmv = a.CtC != nullptr;
-        if (symPath() && fusedIterEnv != 0 && a.pre && !this->slab.active && (!lmv || (a.b && a.q))) {
-            const long n = 6 * A.N, nPad = (n + 3) / 4 * 4;
-            const int g = symGrid();      // the gather's grid and vertex -> XCD mapping (XcdWalk)
-            const int fx = symXcd && g % 8 == 0;
-            if (a.first) {      // the solver adopts rNew / pNew after every launch: the start state moves there unchanged
-                HIP_CHECK(hipMemcpyAsync(a.rNew, a.rOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
-                HIP_CHECK(hipMemcpyAsync(a.pNew, a.pOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
-                ScopedKernel k(ctx, "packVertexRecords"); arap_packPlanes<T><<<vgrid(), kBlock, 0, ctx.stream>>>(a.pNew, planes, A.N);
-            } else if (lmv) {
-                ScopedKernel k(ctx, "PCGStep2+PCGStep3");
-                const ArapLmStep L{a.b, a.deltaOut ? a.deltaOut : a.delta, a.q->partials, a.qTag, a.afterReset, a.betaNum.partials, a.betaNum.n, a.betaDen.partials, a.betaDen.n};
-                arap_flatStepPlanes<T, true><<<g, kBlock, 0, ctx.stream>>>(planes, A.N, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n, a.aDenPrev.partials, a.aDenPrev.n,
-                                                                       a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L, fx, flatBackward);
-                if (!a.afterReset) a.q->n = g;
-            } else {
-                ScopedKernel k(ctx, "PCGStep2+PCGStep3");
-                arap_flatStepPlanes<T, false><<<g, kBlock, 0, ctx.stream>>>(planes, A.N, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n, a.aDenPrev.partials, a.aDenPrev.n,
-                                                                        a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, ArapLmStep{}, fx, flatBackward);
-            }
-            ScopedKernel k(ctx, "PCGStep1");
-            const int gs = launchSym(a.pNew, a.ApNew, a.CtC, a.aDen, ctx, ArapIterSums{a.rNew, a.pre, a.aNum->partials, a.s2->partials, a.s3->partials});
-            a.aNum->n = a.aDen->n = a.s2->n = a.s3->n = gs;
-            return true;
-        }
-        return false;
+        // Gauss-Newton and (round 6) Levenberg-Marquardt: a.CtC adds CtC p to the gather, the flat pass carries b, Q and the restart after a residual reset (LmStep)
+        if (!symPath() || fusedIterEnv == 0 || !a.pre || this->slab.active || (a.CtC && !(a.b && a.q))) return false;
+        const long n = 6 * A.N, nPad = (n + 3) / 4 * 4;
+        const int g = symGrid();      // the gather's grid and vertex -> XCD mapping (XcdWalk)
+        const int fx = symXcd && g % 8 == 0;
+        pcgTwoLaunchIteration(a, nPad, ctx,
+            [&] { ScopedKernel k(ctx, "packVertexRecords"); arap_packPlanes<T><<<vgrid(), kBlock, 0, ctx.stream>>>(a.pNew, planes, A.N); },
+            [&](bool lm, const LmStep<T>& L) {
+                (lm ? arap_flatStepPlanes<T, true> : arap_flatStepPlanes<T, false>)<<<g, kBlock, 0, ctx.stream>>>(planes, A.N, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
+                    a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L, fx, flatBackward);
+                return g;
+            },
+            [&](const IterSums<T>& S) { return launchSym(a.pNew, a.ApNew, a.CtC, a.aDen, ctx, S); });
+        return true;
     }
     // ---- the whole linear solve in ONE workgroup (arap_onchip.h; solver parameter amd_onchip = 5): symmetric graphs within the ELL width whose vertices fit a variant ----
     OnchipGuard ocGuard;      // the switches (OPT_AMD_ONCHIP = 0) and the failure word of the guarded update -- one this kernel never sets: it has no wait that could time out
@@ -999,14 +885,7 @@ struct ArapOps : EnergyOps<T> {
             ScopedKernel k(ctx, "PCGSolveOnChip");
             if (hipLaunchKernel(o->fn, dim3(1), dim3(threads), kargs, (size_t)threads * o->v * o->lds, ctx.stream) != hipSuccess) { (void)hipGetLastError(); ocGuard.enabled = false; return false; }
         }
-        if (!lm) {      // PCGLinearUpdate X += delta, guarded as ocApplyDelta guards it (LM: the solver applies the update itself)
-            ScopedKernel k(ctx, "PCGLinearUpdate");
-            for (size_t i = 0; i < this->unknowns.size(); ++i) {
-                const auto& u = this->unknowns[i];
-                const long cnt = u.elems * u.channels;
-                ocApplyDelta<T><<<(int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, 64)), kBlock, 0, ctx.stream>>>(unknownPtr((int)i), delta + u.offset, cnt, ocGuard.bad, ocGuard.hostErr);
-            }
-        }
+        if (!lm) ocApplyDeltaToUnknowns(*this, delta, 64, ocGuard, ctx);      // PCGLinearUpdate X += delta, guarded (LM: the solver applies the update itself)
         ocGuard.launched = true;
         return true;
     }

@@ -16,7 +16,7 @@
 // members N, nE, vidx[V], X[NIMG]; host bindParams(void**), unknownParam(img).
 #pragma once
 #include "stencil_engine.h"
-#include "graph_common.h"
+#include "graph_pcg.h"
 #include <hipcub/hipcub.hpp>
 
 namespace optamd {
@@ -237,15 +237,13 @@ __device__ __forceinline__ void ge_slotDispatch(int j, const G& g, const GOff<G>
         else if constexpr (J + 1 < G::V) ge_slotDispatch<T, G, J + 1>(j, g, vo, vec, e, q, jp2);
     }
 }
-// S.r != nullptr: the launch is the Step1 half of a two-kernel PCG iteration; besides p . A p it sums, at the vertex, alphaNumerator = sum M r^2 and the two sums of
-// the expanded beta numerator, s2 = sum M r . A p and s3 = sum M (A p)^2 (energy.h PcgIterArgs), from the r and M = pre it is handed.
-template <class T> struct GeIterSums { const T* r; const T* M; double *aNum, *s2, *s3; };
 // out = J^T J vec (LM: + CtC vec) without records: ge_vertices<T, G, 3, GE_GATHER_LANES> with every record it would load evaluated in place -- the same lane split,
 // the same ascending walk of the incidence list, the same shuffle fold, hence the same bits in `out`.  The edges' share of p . A p, |J p|^2 per hyperedge, is
-// counted once: at the hyperedge's slot-0 entry.
+// counted once: at the hyperedge's slot-0 entry.  S.r != nullptr: the launch is the Step1 half of a two-launch PCG iteration and adds the sums of graph_pcg.h IterSums,
+// term by term, from the r and M = pre it is handed.
 template <class T, class G, bool LM>
 __global__ __launch_bounds__(kBlock) void ge_gather(G g, const T* __restrict__ vec, GOff<G> vo, T* __restrict__ out, const T* __restrict__ CtC, double* __restrict__ partials,
-                                                     Incidence inc, GeIterSums<T> S) {
+                                                     Incidence inc, IterSums<T> S) {
     constexpr int LANES = GE_GATHER_LANES;
     __shared__ double scratch[4 * (kBlock / kWave + 1)];
     double acc = 0, accNum = 0, acc2 = 0, acc3 = 0;
@@ -289,49 +287,23 @@ __global__ __launch_bounds__(kBlock) void ge_gather(G g, const T* __restrict__ v
             for (int k = 0; k < G::K; ++k) {
                 const long u = unknownIndex<T, G>(vo, v, k);
                 out[u] = gs[k];
-                if (S.r) {
-                    const double m = (double)S.M[u], rr = (double)S.r[u], a = (double)gs[k];
-                    accNum += (m * rr) * rr; acc2 += (m * rr) * a; acc3 += (m * a) * a;
-                }
+                if (S.r) { const double m = (double)S.M[u], rr = (double)S.r[u], a = (double)gs[k]; accNum += iterTerm(m, rr, rr); acc2 += iterTerm(m, rr, a); acc3 += iterTerm(m, a, a); }
             }
         }
     }
-    if (S.r) {
-        double vv[4] = {acc, accNum, acc2, acc3};
-        blockReduceSumN<4>(vv, scratch);
-        if (threadIdx.x == 0) { if (partials) partials[blockIdx.x] = vv[0]; S.aNum[blockIdx.x] = vv[1]; S.s2[blockIdx.x] = vv[2]; S.s3[blockIdx.x] = vv[3]; }
-        return;
-    }
+    if (S.r) { double vv[4] = {acc, accNum, acc2, acc3}; storeIterSums(vv, partials, S, scratch); return; }
     const double t = blockReduceSum(acc, scratch);
     if (threadIdx.x == 0 && partials) partials[blockIdx.x] = t;
 }
 
-// PCGStep2 + PCGStep3 of the previous iteration in one flat pass over the padded scalars, alpha and beta from the previous launch's partial sums (beta's numerator by
-// the expansion of energy.h PcgIterArgs, clamped at 0; the reference's guards, solver.t:456-459, 544-547).  Energy-independent: arap_flatStepPlanes without the planes.
-// LM: delta goes to deltaOut (the solver enqueues the next launch before it has read Q), Q_{k-1} = 1/2 sum delta . (r + b) (solver.t:483-485) leaves as per-workgroup
-// partials (tagged words if qTag != 0), and after a split residual reset (afterReset: delta and r are already the new ones, solver.t:1077-1083) the pass only forms
-// p = M r + beta p with beta = sum bNum / sum bDen.
-template <class T> struct GeLmStep { const T* b; T* deltaOut; double* q; unsigned qTag; int afterReset; const double* bNumP; int nbNum; const double* bDenP; int nbDen; };
+// PCGStep2 + PCGStep3 of the previous iteration in one flat pass over the padded scalars: the scalars of graph_flat_scalars.inc, LM's extras of graph_pcg.h (LmStep), the
+// update in a grid-stride loop.  Energy-independent: arap_flatStepPlanes without the planes.
 template <class T, bool LM>
 __global__ __launch_bounds__(kBlock) void ge_flatStep(long n, T* __restrict__ delta, const T* __restrict__ pOld, const T* __restrict__ rOld, const T* __restrict__ Ap, const T* __restrict__ M,
                                                        T* __restrict__ rNew, T* __restrict__ pNew, const double* aNumP, int nNum, const double* aDenP, int nDen,
-                                                       const double* s2P, int n2, const double* s3P, int n3, GeLmStep<T> L) {
+                                                       const double* s2P, int n2, const double* s3P, int n3, LmStep<T> L) {
     __shared__ double scratch[4 * (kBlock / kWave + 1)];
-    T alpha, beta;
-    const bool restart = LM && L.afterReset;
-    if (restart) {
-        const double* const ps[2] = {L.bNumP, L.bDenP}; const int ns[2] = {L.nbNum, L.nbDen}; double o2[2];
-        sumPartialsN<2>(ps, ns, scratch, o2);
-        const T bNum = (T)o2[0], bDen = (T)o2[1];
-        alpha = T(0); beta = (bDen > T(0)) ? bNum / bDen : T(0);                            // PCGStep3's guard (solver.t:544-547)
-    } else {
-        const double* const ps[4] = {aNumP, aDenP, s2P, s3P}; const int ns[4] = {nNum, nDen, n2, n3}; double o4[4];
-        sumPartialsN<4>(ps, ns, scratch, o4);
-        const T aNum = (T)o4[0], aDen = (T)o4[1];
-        alpha = (aDen > T(0)) ? aNum / aDen : T(0);                                          // solver.t:456-459
-        const double bNumD = fmax(o4[0] - 2.0 * (double)alpha * o4[2] + (double)alpha * (double)alpha * o4[3], 0.0);
-        beta = (aNum > T(0)) ? (T)bNumD / aNum : T(0);                                       // solver.t:544-547
-    }
+#include "graph_flat_scalars.inc"      // alpha, beta, restart
     T* const dOut = LM ? L.deltaOut : delta;
     double accQ = 0;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -430,34 +402,23 @@ struct GraphOps : EnergyOps<T> {
         return nullptr;
     }
     bool fusedOn() const { return this->graphFused && !fusedWhyNot(); }
-    int launchGather(const T* v, T* out, const T* CtC, double* dotPartials, const GeIterSums<T>& S, LaunchCtx& ctx) {
+    int launchGather(const T* v, T* out, const T* CtC, double* dotPartials, const IterSums<T>& S, LaunchCtx& ctx) {
         const int gv = vgrid(GE_GATHER_LANES);
         if (CtC) ge_gather<T, G, true><<<gv, kBlock, 0, ctx.stream>>>(g, v, vo, out, CtC, dotPartials, incidence(), S);
         else ge_gather<T, G, false><<<gv, kBlock, 0, ctx.stream>>>(g, v, vo, out, nullptr, dotPartials, incidence(), S);
         return gv;
     }
     bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
-        const bool lmv = a.CtC != nullptr;
-        if (!fusedOn() || !a.pre || this->slab.active || (lmv && !(a.b && a.q))) return false;
+        if (!fusedOn() || !a.pre || this->slab.active || (a.CtC && !(a.b && a.q))) return false;
         const long nPad = (this->nScalars + 3) / 4 * 4;      // the solver's vectors (zero beyond nScalars)
         const int gf = flatGrid(nPad, cus, kMaxPartials / 2);
-        if (a.first) {      // the solver adopts rNew / pNew after every launch: the start state moves there unchanged
-            HIP_CHECK(hipMemcpyAsync(a.rNew, a.rOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
-            HIP_CHECK(hipMemcpyAsync(a.pNew, a.pOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
-        } else if (lmv) {
-            ScopedKernel k(ctx, "PCGStep2+PCGStep3");
-            const GeLmStep<T> L{a.b, a.deltaOut ? a.deltaOut : a.delta, a.q->partials, a.qTag, a.afterReset, a.betaNum.partials, a.betaNum.n, a.betaDen.partials, a.betaDen.n};
-            ge_flatStep<T, true><<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n, a.aDenPrev.partials, a.aDenPrev.n,
-                                                                a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L);
-            if (!a.afterReset) a.q->n = gf;
-        } else {
-            ScopedKernel k(ctx, "PCGStep2+PCGStep3");
-            ge_flatStep<T, false><<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n, a.aDenPrev.partials, a.aDenPrev.n,
-                                                                 a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, GeLmStep<T>{});
-        }
-        ScopedKernel k(ctx, "PCGStep1");
-        const int gv = launchGather(a.pNew, a.ApNew, a.CtC, a.aDen->partials, GeIterSums<T>{a.rNew, a.pre, a.aNum->partials, a.s2->partials, a.s3->partials}, ctx);
-        a.aNum->n = a.aDen->n = a.s2->n = a.s3->n = gv;
+        pcgTwoLaunchIteration(a, nPad, ctx, [] {},
+            [&](bool lm, const LmStep<T>& L) {
+                (lm ? ge_flatStep<T, true> : ge_flatStep<T, false>)<<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
+                    a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L);
+                return gf;
+            },
+            [&](const IterSums<T>& S) { return launchGather(a.pNew, a.ApNew, a.CtC, a.aDen->partials, S, ctx); });
         return true;
     }
     std::string describe(int, bool lmv, const OnChipLm<T>*) override {      // ("key=value; ..." -- no ';' inside a value)
@@ -472,7 +433,7 @@ struct GraphOps : EnergyOps<T> {
     void applyJTJ(const T* v, T* out, const T* CtC, Reduction* dot, LaunchCtx& ctx) override {
         if (fusedOn()) {      // one launch instead of two, the same bits in `out`
             ScopedKernel k(ctx, "PCGStep1");
-            const int gv = launchGather(v, out, CtC, dot ? dot->partials : nullptr, GeIterSums<T>{nullptr, nullptr, nullptr, nullptr, nullptr}, ctx);
+            const int gv = launchGather(v, out, CtC, dot ? dot->partials : nullptr, IterSums<T>{nullptr, nullptr, nullptr, nullptr, nullptr}, ctx);
             if (dot) dot->n = gv;
             return;
         }

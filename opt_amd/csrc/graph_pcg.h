@@ -1,0 +1,86 @@
+// What the PCG kernels of the graph kernel sets share, each piece written once: the value types and derivative columns of ARAP's gather (arap_applyEll, arap_onchipPcg;
+// the body of the walk is arap_half_edge_pair.inc), the argument structs, the term and the store of the sums of a two-launch iteration (arap_applyEll, ge_gather,
+// arap_onchipPcg), LM's extras of the flat PCGStep2 + PCGStep3 pass (arap_flatStepPlanes, ge_flatStep; its scalars are graph_flat_scalars.inc) and the host side of
+// such an iteration (ArapOps::pcgIteration, GraphOps::pcgIteration).  Every device piece is a force-inlined function on plain values; a kernel keeps its own loop, layout,
+// grid and walk order, and the order in which it adds the terms it gets from here.  No pragma in this file: it is compiled with the contraction setting of the file
+// that includes it (energy_graph_functors.hip: off).  Every kernel but arap_applyFused, which lost dead code, compiles to the instructions it had before these pieces
+// were shared; what else was tried as a function, and what the compiler made of it: profiles/graph_shared_text.md.
+#pragma once
+#include "graph_common.h"
+
+namespace optamd {
+namespace {
+
+template <class T> struct V3 { T x, y, z; };
+template <class T> __device__ __forceinline__ T dot3(const V3<T>& a, const V3<T>& b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+template <class T> __device__ __forceinline__ V3<T> ldv3(const T* p, long i) { return reinterpret_cast<const V3<T>*>(p)[i]; }      // one 12 / 24-byte load
+template <class T> __device__ __forceinline__ void stv3(T* p, long i, const V3<T>& v) { reinterpret_cast<V3<T>*>(p)[i] = v; }
+template <class T> struct alignas(16) Q4 { T a, b, c, d; };      // an entry of a 16-byte (double: 32-byte) SoA plane
+
+// ---- ARAP: J^T J p at a vertex -------------------------------------------------------------------------------------------------------------------------------
+template <class T> struct ArapCoef { T a0, a1, a2, a3, a4, a5, b0, b1, b2, b3, b4, b5, b6, b7, b8, c0, c1, c2, c3, c4, c5; };
+// the non-zero entries of dR3/d alpha, d beta, d gamma (arap_rot's coefficients, same products)
+template <class T>
+__device__ __forceinline__ ArapCoef<T> arap_coef(T sa, T ca, T sb, T cb, T sg, T cg) {
+    ArapCoef<T> c;
+    c.a0 = sg * sa + cg * sb * ca;  c.a1 = sg * ca - cg * sb * sa;
+    c.a2 = -cg * sa + sg * sb * ca; c.a3 = -cg * ca - sg * sb * sa;
+    c.a4 = cb * ca;                 c.a5 = -cb * sa;
+    c.b0 = -cg * sb; c.b1 = cg * cb * sa; c.b2 = cg * cb * ca;
+    c.b3 = -sg * sb; c.b4 = sg * cb * sa; c.b5 = sg * cb * ca;
+    c.b6 = -cb;      c.b7 = -sb * sa;     c.b8 = -sb * ca;
+    c.c0 = -sg * cb; c.c1 = -cg * ca - sg * sb * sa; c.c2 = cg * sa - sg * sb * ca;
+    c.c3 = cg * cb;  c.c4 = -sg * ca + cg * sb * sa; c.c5 = sg * sa + cg * sb * ca;
+    return c;
+}
+template <class T>
+__device__ __forceinline__ void arap_cols(const ArapCoef<T>& c, const V3<T>& u, V3<T>& D0, V3<T>& D1, V3<T>& D2) {
+    D0.x = c.a0 * u.y + c.a1 * u.z; D0.y = c.a2 * u.y + c.a3 * u.z; D0.z = c.a4 * u.y + c.a5 * u.z;
+    D1.x = c.b0 * u.x + c.b1 * u.y + c.b2 * u.z; D1.y = c.b3 * u.x + c.b4 * u.y + c.b5 * u.z; D1.z = c.b6 * u.x + c.b7 * u.y + c.b8 * u.z;
+    D2.x = c.c0 * u.x + c.c1 * u.y + c.c2 * u.z; D2.y = c.c3 * u.x + c.c4 * u.y + c.c5 * u.z; D2.z = 0;
+}
+// ---- the sums of a two-launch PCG iteration ----------------------------------------------------------------------------------------------------------------------
+// S.r != nullptr: the gather is the Step1 half of a two-launch iteration ([flat PCGStep2 + PCGStep3 pass] + [gather]; EnergyOps::pcgIteration).  Besides p . A p it then
+// sums, at the lane that owns the vertex, what the next flat pass needs -- alphaNumerator = sum M r^2 and the two sums of the expanded beta numerator, s2 = sum M r . A p and
+// s3 = sum M (A p)^2 (energy.h PcgIterArgs), every term from M, r, A p themselves in double (exact products of floats; see energy_image_warping.hip dprod3) -- so that
+// PCGStep2 and PCGStep3 become one flat pass without a reduction between them.
+template <class T> struct IterSums { const T* r; const T* M; double *aNum, *s2, *s3; };
+template <class T> __device__ __forceinline__ double iterTerm(T m, T a, T b) { return ((double)m * (double)a) * (double)b; }
+// the end of such a gather: vv = {p . A p, aNum, s2, s3} over the workgroup, one partial each.  scratch: 4 * blockDim / 64 doubles.  (vv is the caller's: with the array
+// inside this function the partial-sum loop of ge_gather came out with its branch turned round)
+template <class T>
+__device__ __forceinline__ void storeIterSums(double (&vv)[4], double* partials, const IterSums<T>& S, double* scratch) {
+    blockReduceSumN<4>(vv, scratch);
+    if (threadIdx.x == 0) { if (partials) partials[blockIdx.x] = vv[0]; S.aNum[blockIdx.x] = vv[1]; S.s2[blockIdx.x] = vv[2]; S.s3[blockIdx.x] = vv[3]; }
+}
+
+// ---- the flat pass: PCGStep2 + PCGStep3 of the previous iteration (solver.t:446-489, 537-550) ---------------------------------------------------------------------------
+// LM (Levenberg-Marquardt): delta goes to deltaOut (the solver enqueues the next launch before it has read Q: an early-out must still find the old delta),
+// Q_{k-1} = 1/2 sum delta . (r + b) (solver.t:483-485) leaves as per-workgroup partials (tagged words if qTag != 0), and after a split residual reset (afterReset: delta
+// and r are already the new ones, solver.t:1077-1083) the pass only forms p = M r + beta p with beta = sum bNum / sum bDen.
+template <class T> struct LmStep { const T* b; T* deltaOut; double* q; unsigned qTag; int afterReset; const double* bNumP; int nbNum; const double* bDenP; int nbDen; };
+// The scalars of the pass -- alpha, beta, restart -- are graph_flat_scalars.inc: text both kernels include, not a function (see there).
+
+// ---- host side of a two-launch iteration -------------------------------------------------------------------------------------------------------------------------------
+// first(): what the first launch of a solve needs besides the start state; flat(lm, L): launches the flat pass and returns its grid; gather(S): launches the gather and
+// returns its grid.  nPad: the scalars of the solver's vectors.
+template <class T, class First, class Flat, class Gather>
+void pcgTwoLaunchIteration(const PcgIterArgs<T>& a, long nPad, LaunchCtx& ctx, First&& first, Flat&& flat, Gather&& gather) {
+    const bool lmv = a.CtC != nullptr;
+    if (a.first) {      // the solver adopts rNew / pNew after every launch: the start state moves there unchanged
+        HIP_CHECK(hipMemcpyAsync(a.rNew, a.rOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
+        HIP_CHECK(hipMemcpyAsync(a.pNew, a.pOld, nPad * sizeof(T), hipMemcpyDeviceToDevice, ctx.stream));
+        first();
+    } else {
+        ScopedKernel k(ctx, "PCGStep2+PCGStep3");
+        const LmStep<T> L = lmv ? LmStep<T>{a.b, a.deltaOut ? a.deltaOut : a.delta, a.q->partials, a.qTag, a.afterReset, a.betaNum.partials, a.betaNum.n, a.betaDen.partials, a.betaDen.n} : LmStep<T>{};
+        const int g = flat(lmv, L);
+        if (lmv && !a.afterReset) a.q->n = g;
+    }
+    ScopedKernel k(ctx, "PCGStep1");
+    const int g = gather(IterSums<T>{a.rNew, a.pre, a.aNum->partials, a.s2->partials, a.s3->partials});
+    a.aNum->n = a.aDen->n = a.s2->n = a.s3->n = g;
+}
+
+}  // namespace
+}  // namespace optamd

@@ -119,15 +119,7 @@ struct OnchipLauncher {
                 return false;
             }
         }
-        if (!lm) {      // (LM: the solver applies the update itself)
-            ScopedKernel k(ctx, "PCGLinearUpdate");
-            for (size_t i = 0; i < ops.unknowns.size(); ++i) {
-                const auto& u = ops.unknowns[i];
-                const long cnt = u.elems * u.channels;
-                const int grid = (int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, updateCap));
-                ocApplyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(ops.unknownPtr((int)i), delta + u.offset, cnt, guard.bad, guard.hostErr);
-            }
-        }
+        if (!lm) ocApplyDeltaToUnknowns(ops, delta, updateCap, guard, ctx);      // (LM: the solver applies the update itself)
         guard.launched = true;
         return true;
     }

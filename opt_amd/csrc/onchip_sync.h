@@ -294,6 +294,17 @@ __global__ __launch_bounds__(kBlock) void ocApplyDelta(T* __restrict__ X, const 
     }
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) X[i] = X[i] + delta[i];
 }
+// ... over every unknown image of the kernel set `ops` (EnergyOps), with at most `cap` workgroups per image
+template <class T, class Ops>
+void ocApplyDeltaToUnknowns(const Ops& ops, const T* delta, long cap, const OnchipGuard& guard, LaunchCtx& ctx) {
+    ScopedKernel k(ctx, "PCGLinearUpdate");
+    for (size_t i = 0; i < ops.unknowns.size(); ++i) {
+        const auto& u = ops.unknowns[i];
+        const long cnt = u.elems * u.channels;
+        const int grid = (int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, cap));
+        ocApplyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(ops.unknownPtr((int)i), delta + u.offset, cnt, guard.bad, guard.hostErr);
+    }
+}
 
 }  // namespace
 }  // namespace optamd

@@ -13,6 +13,7 @@
 //    rotation written by workgroup 0 of Step3.
 #include "solver.h"
 #include "onchip_sync.h"
+#include "pcg_flat_kernels.h"
 #include <chrono>
 #include <mutex>
 #include <cmath>
@@ -29,276 +30,6 @@ static inline void cpuRelax() {
 }
 
 namespace optamd {
-
-// ------------------------------------------------------------------------------------------------------
-// 16-byte packs of opt_float
-template <class T> struct Pack;
-template <> struct alignas(16) Pack<float> { float v[4]; };
-template <> struct alignas(16) Pack<double> { double v[2]; };
-template <class T> struct PackN;
-template <> struct PackN<float> { static constexpr int N = 4; typedef float vec __attribute__((ext_vector_type(4))); };
-template <> struct PackN<double> { static constexpr int N = 2; typedef double vec __attribute__((ext_vector_type(2))); };
-
-// Streaming (non-temporal) 16-byte accesses: every PCG vector is far larger than L2 + Infinity Cache and is
-// touched once per kernel, so the hot streaming kernels ask the memory system not to retain the lines.
-// Measured on MI355X (tools/microbench_stream.hip, PCGStep2 shape at 4096^2): plain 302 us, nt + 2 packs in
-// flight per lane 270 us.
-#ifndef S2_NT_LOAD
-#define S2_NT_LOAD 1
-#endif
-template <class T> __device__ __forceinline__ Pack<T> ldnt(const T* base, long i) {
-    typedef typename PackN<T>::vec V;
-    const V v = S2_NT_LOAD ? __builtin_nontemporal_load((const V*)base + i) : ((const V*)base)[i];
-    Pack<T> p;
-#pragma unroll
-    for (int k = 0; k < PackN<T>::N; ++k) p.v[k] = v[k];
-    return p;
-}
-template <class T> __device__ __forceinline__ void stnt(T* base, long i, const Pack<T>& p) {
-    typedef typename PackN<T>::vec V;
-    V v;
-#pragma unroll
-    for (int k = 0; k < PackN<T>::N; ++k) v[k] = p.v[k];
-    __builtin_nontemporal_store(v, (V*)base + i);
-}
-
-template <class T> __device__ __forceinline__ T guardedInvert(T x) {   // solver.t:323-332 (CERES)
-    T s = T(1) + sqrt(x);
-    return T(1) / (s * s);
-}
-
-// PCGInit1 (non-graph tail) / PCGInit1_Finish (graph): solver.t:384-392, 399-419.  r already holds -J^T F.
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_initFinish(const T* __restrict__ r, const T* __restrict__ diag, T* __restrict__ pre,
-                                                       T* __restrict__ p, T* __restrict__ delta, long nPacks, int usePre, int graphMode,
-                                                       double* __restrict__ partials) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    constexpr int N = PackN<T>::N;
-    double acc = 0;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nPacks; i += (long)gridDim.x * blockDim.x) {
-        Pack<T> R = ((const Pack<T>*)r)[i], D = ((const Pack<T>*)diag)[i], PR, PP, Z;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            T d = usePre ? D.v[k] : T(1);
-            T pr = guardedInvert(d);
-            if (graphMode && !usePre) pr = T(1);
-            T pp = pr * R.v[k];
-            PR.v[k] = pr; PP.v[k] = pp; Z.v[k] = T(0);
-            acc += (double)(R.v[k] * pp);
-        }
-        ((Pack<T>*)pre)[i] = PR; ((Pack<T>*)p)[i] = PP; ((Pack<T>*)delta)[i] = Z;
-    }
-    double t = blockReduceSum(acc, scratch);
-    if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-
-// total[0] = sum(partials[0..n))   (one workgroup)
-__global__ __launch_bounds__(kBlock) void k_finalizeSum(const double* __restrict__ partials, int n, double* __restrict__ total) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    double s = sumPartials(partials, n, scratch);
-    if (threadIdx.x == 0) total[0] = s;
-}
-
-// total[k] = sum(partials_k[0..n_k)) for four reductions at once: workgroup k handles array k (slab mode: one launch
-// before the single 4-double all-reduce of the fused PCG iteration)
-struct Partials4 { const double* p[4]; int n[4]; };
-__global__ __launch_bounds__(kBlock) void k_finalizeSum4(Partials4 in, double* __restrict__ total) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    double s = sumPartials(in.p[blockIdx.x], in.n[blockIdx.x], scratch);
-    if (threadIdx.x == 0) total[blockIdx.x] = s;
-}
-
-// PCGStep2: solver.t:446-489
-template <class T, bool LM>
-__global__ __launch_bounds__(kBlock) void k_step2(T* __restrict__ delta, const T* __restrict__ p, T* __restrict__ r, const T* __restrict__ Ap,
-                                                  const T* __restrict__ pre /*nullptr -> 1*/, const T* __restrict__ b, T* __restrict__ z, long nPacks,
-                                                  const double* __restrict__ aNumTotal, const double* __restrict__ aDenPartials, int nDen,
-                                                  double* __restrict__ bNumPartials, double* __restrict__ qPartials) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    constexpr int N = PackN<T>::N;
-    const T aDen = (T)sumPartials(aDenPartials, nDen, scratch);
-    const T aNum = (T)aNumTotal[0];
-    const T alpha = (aDen > T(0)) ? aNum / aDen : T(0);   // guardDivisionByZero, solver.t:456-459
-    double accB = 0, accQ = 0;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i0 = blockIdx.x * (long)blockDim.x + threadIdx.x; i0 < nPacks; i0 += 2 * stride) {
-        // two packs per lane in flight: issue all loads of both before the first use
-        Pack<T> D[2], P[2], R[2], A[2], M[2], B[2], Z;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const long i = i0 + u * stride;
-            if (i < nPacks) {
-                D[u] = ldnt(delta, i); P[u] = ldnt(p, i); R[u] = ldnt(r, i); A[u] = ldnt(Ap, i);
-                if (pre) M[u] = ldnt(pre, i);
-                if (LM) B[u] = ldnt(b, i);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const long i = i0 + u * stride;
-            if (i < nPacks) {
-#pragma unroll
-                for (int k = 0; k < N; ++k) {
-                    T dl = D[u].v[k] + alpha * P[u].v[k];
-                    T rr = R[u].v[k] - alpha * A[u].v[k];
-                    T m = pre ? M[u].v[k] : T(1);
-                    T zz = m * rr;
-                    D[u].v[k] = dl; R[u].v[k] = rr; Z.v[k] = zz;
-                    accB += (double)(zz * rr);
-                    if (LM) accQ += (double)(T(0.5) * (dl * (rr + B[u].v[k])));
-                }
-                stnt(delta, i, D[u]); stnt(r, i, R[u]); stnt(z, i, Z);      // non-temporal: nothing of this pass is read again before the next one has streamed past it
-            }
-        }
-    }
-    double t = blockReduceSum(accB, scratch);
-    if (threadIdx.x == 0) bNumPartials[blockIdx.x] = t;
-    if (LM) {
-        double tq = blockReduceSum(accQ, scratch);
-        if (threadIdx.x == 0) qPartials[blockIdx.x] = tq;
-    }
-}
-
-// PCGStep2_1stHalf: solver.t:491-503
-// deltaOut may be delta (in place) or another vector (the caller then decides later which of the two it keeps).  alphaNumerator is either a
-// finished total (aNumTotal, nNum == 0) or partial sums this kernel adds up itself -- the same sumPartials over kBlock threads as
-// k_finalizeSum, so the same bits, one launch less.
-// pOwed / alphaOwed (may be null): a term alphaOwed[0] * pOwed that an earlier launch left owed to delta (PcgIterResult::owedP) is added first -- the reference's
-// order of additions, one pass instead of two.
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_step2FirstHalf(const T* delta, T* deltaOut, const T* __restrict__ p, long nPacks, const double* __restrict__ aNumTotal,
-                                                           const double* __restrict__ aNumPartials, int nNum, const double* __restrict__ aDenPartials, int nDen,
-                                                           const T* __restrict__ pOwed = nullptr, const T* __restrict__ alphaOwed = nullptr) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    constexpr int N = PackN<T>::N;
-    const T aDen = (T)sumPartials(aDenPartials, nDen, scratch);
-    const T aNum = nNum > 0 ? (T)sumPartials(aNumPartials, nNum, scratch) : (T)aNumTotal[0];
-    const T alpha = (aDen > T(0)) ? aNum / aDen : T(0);
-    const T a2 = pOwed ? alphaOwed[0] : T(0);
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nPacks; i += (long)gridDim.x * blockDim.x) {
-        Pack<T> D = ((const Pack<T>*)delta)[i], P = ((const Pack<T>*)p)[i];
-        if (pOwed) {
-            const Pack<T> P2 = ((const Pack<T>*)pOwed)[i];
-#pragma unroll
-            for (int k = 0; k < N; ++k) D.v[k] = D.v[k] + a2 * P2.v[k];
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) D.v[k] = D.v[k] + alpha * P.v[k];
-        ((Pack<T>*)deltaOut)[i] = D;
-    }
-}
-
-// Completion stamp for PcgSolver::drain(): everything enqueued before it has finished when the host sees the value.
-__global__ void k_stamp(unsigned long long* flag, unsigned long long v) {
-    if (threadIdx.x == 0) __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// PCGStep2_2ndHalf: solver.t:505-534
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_step2SecondHalf(const T* __restrict__ delta, T* __restrict__ r, const T* __restrict__ Adelta, const T* __restrict__ b,
-                                                            const T* __restrict__ pre, T* __restrict__ z, long nPacks, double* __restrict__ bNumPartials,
-                                                            double* __restrict__ qPartials) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    constexpr int N = PackN<T>::N;
-    double accB = 0, accQ = 0;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nPacks; i += (long)gridDim.x * blockDim.x) {
-        Pack<T> D = ((const Pack<T>*)delta)[i], A = ((const Pack<T>*)Adelta)[i], B = ((const Pack<T>*)b)[i], M, R, Z;
-        if (pre) M = ((const Pack<T>*)pre)[i];
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            T rr = B.v[k] - A.v[k];
-            T m = pre ? M.v[k] : T(1);
-            T zz = m * rr;
-            R.v[k] = rr; Z.v[k] = zz;
-            accB += (double)(zz * rr);
-            accQ += (double)(T(0.5) * (D.v[k] * (rr + B.v[k])));
-        }
-        ((Pack<T>*)r)[i] = R; ((Pack<T>*)z)[i] = Z;
-    }
-    double t = blockReduceSum(accB, scratch);
-    if (threadIdx.x == 0) bNumPartials[blockIdx.x] = t;
-    double tq = blockReduceSum(accQ, scratch);
-    if (threadIdx.x == 0) qPartials[blockIdx.x] = tq;
-}
-
-// PCGStep3: solver.t:537-550; workgroup 0 also publishes betaNumerator as the next alphaNumerator (:1091)
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_step3(const T* __restrict__ z, T* __restrict__ p, long nPacks, const double* __restrict__ bNumPartials, int nB,
-                                                  const double* __restrict__ aNumOld, double* __restrict__ aNumNext) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    constexpr int N = PackN<T>::N;
-    const double bSum = sumPartials(bNumPartials, nB, scratch);
-    const T rDotzNew = (T)bSum, rDotzOld = (T)aNumOld[0];
-    const T beta = (rDotzOld > T(0)) ? rDotzNew / rDotzOld : T(0);
-    if (blockIdx.x == 0 && threadIdx.x == 0) aNumNext[0] = bSum;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nPacks; i += (long)gridDim.x * blockDim.x) {
-        Pack<T> Z = ((const Pack<T>*)z)[i], P = ((Pack<T>*)p)[i];
-#pragma unroll
-        for (int k = 0; k < N; ++k) P.v[k] = Z.v[k] + beta * P.v[k];
-        ((Pack<T>*)p)[i] = P;
-    }
-}
-
-// PCGLinearUpdate / revertUpdate / savePreviousUnknowns on one unknown image (caller-owned array, not padded)
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_axpyImage(T* __restrict__ X, const T* __restrict__ d, long n) {   // X += d   (solver.t:552-557)
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) X[i] = X[i] + d[i];
-}
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_saveAndUpdate(T* __restrict__ X, T* __restrict__ prev, const T* __restrict__ d, long n) {   // prev = X; X += d  (LM: solver.t:1113-1114 in one pass)
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) { const T x = X[i]; prev[i] = x; X[i] = x + d[i]; }
-}
-template <class T>
-__global__ __launch_bounds__(kBlock) void k_copy(T* __restrict__ dst, const T* __restrict__ src, long n) {    // solver.t:559-564, 573-578, 624-629
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) dst[i] = src[i];
-}
-
-// PCGComputeCtC + PCGFinalizeDiagonal: solver.t:616-622, 631-664.  On entry CtC holds raw diag(J^T J).
-// INIT: the kernel also does what PCGInit1's tail does in an LM step before it (k_initFinish: delta = 0, the guarded-inverse preconditioner -- needed only to
-// seed SSq at the first outer iteration, solver.t:635 -- and a p that this kernel overwrites anyway): one pass over the vectors instead of two or three.
-template <class T, bool INIT>
-__global__ __launch_bounds__(kBlock) void k_finalizeDiagonal(T* __restrict__ CtC, T* __restrict__ SSq, const T* __restrict__ r, T* __restrict__ delta,
-                                                             T* __restrict__ pre, T* __restrict__ b, T* __restrict__ p, long nPacks, T radius, T minLm, T maxLm,
-                                                             double* __restrict__ dPartials, double* __restrict__ qPartials, int usePre, int graphMode, int saveSSq) {
-    __shared__ double scratch[kBlock / kWave + 1];
-    constexpr int N = PackN<T>::N;
-    const T invRadius = T(1) / radius;
-    double accD = 0, accQ = 0;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nPacks; i += (long)gridDim.x * blockDim.x) {
-        Pack<T> C = ((Pack<T>*)CtC)[i], R = ((const Pack<T>*)r)[i], S, D, M, P;
-        if (INIT) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                T pr = guardedInvert(usePre ? C.v[k] : T(1));      // k_initFinish
-                if (graphMode && !usePre) pr = T(1);
-                S.v[k] = pr; D.v[k] = T(0);
-            }
-            if (saveSSq) ((Pack<T>*)SSq)[i] = S;                   // PCGSaveSSq (first outer iteration)
-            else S = ((const Pack<T>*)SSq)[i];
-            ((Pack<T>*)delta)[i] = D;
-        } else { S = ((const Pack<T>*)SSq)[i]; D = ((const Pack<T>*)delta)[i]; }
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            T unclamped = C.v[k] * invRadius;                 // computeCtC: diag(J^T J) / radius (o.t:2277-2279)
-            T invS = T(1) / S.v[k];
-            T clampMul = invS / radius;
-            T lo = minLm * clampMul, hi = maxLm * clampMul;
-            T c = fmin(fmax(unclamped, lo), hi);
-            C.v[k] = c;
-            T m = T(1) / (c + radius * unclamped);
-            M.v[k] = m;
-            T pp = m * R.v[k];
-            P.v[k] = pp;
-            accD += (double)(R.v[k] * pp);
-            accQ += (double)(T(0.5) * (D.v[k] * (R.v[k] + R.v[k])));
-        }
-        ((Pack<T>*)CtC)[i] = C; ((Pack<T>*)pre)[i] = M; ((Pack<T>*)b)[i] = R; ((Pack<T>*)p)[i] = P;
-    }
-    double t = blockReduceSum(accD, scratch);
-    if (threadIdx.x == 0) dPartials[blockIdx.x] = t;
-    double tq = blockReduceSum(accQ, scratch);
-    if (threadIdx.x == 0) qPartials[blockIdx.x] = tq;
-}
 
 // ------------------------------------------------------------------------------------------------------
 template <class T>
@@ -319,7 +50,14 @@ struct PcgSolver : SolverBase {
     bool oneKernel = true;              // OPT_AMD_ONEKERNEL=0: use the Step1(+3)/Step2 pair instead of one kernel per PCG iteration
     bool oneKernelLM = true;            // OPT_AMD_ONEKERNEL_LM=0: the same switch for the Levenberg-Marquardt loop only
     Reduction setS[2][4];               // ping-pong {alphaNum, alphaDen, s2, s3} of the single-kernel iteration
-    bool unknownsUpdated = false;       // this step's PCGLinearUpdate was folded into the end of the PCG loop (EnergyOps::finishUpdate)
+    // What a linear solve reports (solveLinear and the paths it tries).  none: the path did not run (of solveLinear: a redo stopped short of the reference-order loop).
+    enum class Path { none, onChip, perIteration, referenceOrder };
+    struct Solved {
+        Path path = Path::none;
+        bool updated = false;           // this step's PCGLinearUpdate was folded into the end of the PCG loop (EnergyOps::finishUpdate, the on-chip Gauss-Newton kernels)
+        explicit operator bool() const { return path != Path::none; }
+        bool onChip() const { return path == Path::onChip; }
+    };
     std::vector<void*> allocs;          // device memory (allocVec, allocRed)
     std::vector<void*> pinned;          // pinned host memory (allocPinned)
     Reduction redA, redB, redQ, redC;   // alpha denominator, beta numerator, q, cost / init numerator
@@ -419,13 +157,14 @@ struct PcgSolver : SolverBase {
         if (onChipFailures <= 3)
             fprintf(stderr, "Opt(amd): a wait inside the on-chip PCG kernel timed out (its workgroups were not co-resident: is the GPU shared?); %s "
                             "with the streaming kernels and the plan stays on them for %d steps before it tries the chip again\n", redo, onChipBackoff);
-        lastStepOnChip = false; usedOnChip = false;
     }
     // a step on the streaming kernels has ended: the back-off is over after onChipBackoff of them, and the next step tries the chip again
     void onChipCleanStep() {
         if (onChipOff() && ++onChipCleanSteps >= onChipBackoff) chip->rearm(stream);
     }
     bool boundForSolve = false;      // bind() has run inside the current Opt_ProblemSolve (SolverBase::insideSolve)
+    bool boundOncePerSolve() const { return insideSolve && boundForSolve && E->bindInvariantDuringSolve(); }      // nothing bind() derives can have changed since init()'s
+    bool gnInitByKernelSet() const { return !lm && !distributed && singleKernelAllowed() && sp.lIterations > 0; }   // PCGInit1 may be the kernel set's own pass (evalJTFInit, evalCostAndJTFInit)
     bool jtfReady = false;           // the pass that computed the last step's cost also ran this step's PCGInit1 (EnergyOps::evalCostAndJTFInit; only inside Opt_ProblemSolve)
     // Where delta lives (round 6).  delta is the one vector the Gauss-Newton loop reads AND writes, and the time of a launch follows the region the allocator put it in
     // (profiles/NOTES.md: 173 / 176 / 191 us at 4096^2 for the same binary in one process, region by region; the ring, the flag bytes and the caller's arrays do not matter).
@@ -492,30 +231,27 @@ struct PcgSolver : SolverBase {
     bool onChipAllowed() const { return !onChipOff() && sp.amd_onchip != 0 && sp.amd_reference_order == 0; }
     bool singleKernelAllowed() const { return oneKernel && sp.amd_reference_order == 0; }
     double* lmBreak = nullptr;          // pinned: {iteration + 1, zeta} of an on-chip LM solve's q early-out (OnChipLm::breakInfo)
-    bool usedOnChip = false, lastStepOnChip = false; double* onChipTrace = nullptr; int onChipTraceCap = 0;      // EnergyOps::pcgSolveOnChip
+    bool lastStepOnChip = false; double* onChipTrace = nullptr; int onChipTraceCap = 0;      // EnergyOps::pcgSolveOnChip
     // true iff `mine` holds on every rank: one all-reduce of a count and one read-back (once per Gauss-Newton step in slab mode)
     bool allRanksAgree(bool mine) {
         hostBuf[0] = mine ? 0.0 : 1.0;
         HIP_CHECK(hipMemcpyAsync(scal + 5, hostBuf, sizeof(double), hipMemcpyHostToDevice, stream));
         comm.allReduceSum(comm.ctx, scal + 5, 1, (void*)stream);
-        HIP_CHECK(hipMemcpyAsync(hostBuf, scal + 5, sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        return hostBuf[0] == 0.0;
+        return readBack(scal + 5, 1)[0] == 0.0;
     }
     // ---- reductions ---------------------------------------------------------------------------------
-    // Host value of a reduction (blocking D2H like the reference's computeCost / fetchQ, solver.t:790-814)
-    double hostSum(const Reduction& R) {
-        if (distributed) {
-            reduceAcross(&R, 1, scal + 2);
-            HIP_CHECK(hipMemcpyAsync(hostBuf, scal + 2, sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            return hostBuf[0];
-        }
-        if (R.hostVisible) { drain(); double s = 0; for (int i = 0; i < R.n; ++i) s += R.partials[i]; return s; }
-        HIP_CHECK(hipMemcpyAsync(hostBuf, R.partials, R.n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    // n doubles of device memory on the host (blocking D2H like the reference's computeCost / fetchQ, solver.t:790-814): valid until the next readBack
+    const double* readBack(const double* dev, int n) {
+        HIP_CHECK(hipMemcpyAsync(hostBuf, dev, n * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        double s = 0; for (int i = 0; i < R.n; ++i) s += hostBuf[i];
-        return s;
+        return hostBuf;
+    }
+    static double sumOf(const double* v, int n) { double s = 0; for (int i = 0; i < n; ++i) s += v[i]; return s; }      // in index order, like every device consumer
+    // Host value of a reduction
+    double hostSum(const Reduction& R) {
+        if (distributed) { reduceAcross(&R, 1, scal + 2); return readBack(scal + 2, 1)[0]; }
+        if (R.hostVisible) { drain(); return sumOf(R.partials, R.n); }
+        return sumOf(readBack(R.partials, R.n), R.n);
     }
     // The same value without draining the stream: begin enqueues the copy and an event, end waits for that event only.
     void beginHostSum(const Reduction& R) {
@@ -535,8 +271,21 @@ struct PcgSolver : SolverBase {
     }
     double endHostSum() {
         HIP_CHECK(hipEventSynchronize(qEvent));
-        double s = 0; for (int i = 0; i < qCount; ++i) s += qSrc[i];
-        return s;
+        return sumOf(qSrc, qCount);
+    }
+    // Spin on pinned memory until arrived() holds.  The stream is queried now and then so that a faulted or never-issued producer ends in the caller's message
+    // instead of a hang: if it reports idle and the value has not been seen, fall back to the runtime's own completion (which also makes the device's writes
+    // to pinned memory visible) and look once more.  false: still missing then.
+    template <class Arrived> bool spinUntil(Arrived arrived) {
+        for (unsigned long spins = 1; !arrived(); ++spins) {
+            if ((spins & 0x3fff) == 0) {
+                const hipError_t e = hipStreamQuery(stream);
+                if (e != hipSuccess && e != hipErrorNotReady) HIP_CHECK(e);
+                if (e == hipSuccess) { HIP_CHECK(hipStreamSynchronize(stream)); return arrived(); }
+            }
+            cpuRelax();
+        }
+        return true;
     }
     // Everything enqueued so far has finished and what it wrote to pinned memory is readable.  A one-thread kernel stamps a pinned word and the host spins
     // on it: no barrier packet with a completion signal in the queue and no wake-up through the runtime (the latency-bound LM steps drain twice or more).
@@ -544,46 +293,23 @@ struct PcgSolver : SolverBase {
         if (!pollSync) { HIP_CHECK(hipStreamSynchronize(stream)); return; }
         const unsigned long long v = ++stampSeq;
         k_stamp<<<1, kWave, 0, stream>>>(stampFlag, v);
-        unsigned long spins = 0;
-        while (__atomic_load_n(stampFlag, __ATOMIC_ACQUIRE) != v) {
-            if ((++spins & 0x3fff) == 0) {
-                const hipError_t e = hipStreamQuery(stream);
-                if (e != hipSuccess && e != hipErrorNotReady) HIP_CHECK(e);
-                // The stream reports idle but the stamp has not been seen: fall back to the runtime's own completion (which also makes the device's
-                // writes to pinned memory visible) and look once more; only a stamp that is still missing then is an error -- and polling is given up
-                // for this plan rather than the process.
-                if (e == hipSuccess) {
-                    HIP_CHECK(hipStreamSynchronize(stream));
-                    if (__atomic_load_n(stampFlag, __ATOMIC_ACQUIRE) != v) {
-                        fprintf(stderr, "Opt(amd): completion stamp %llu not visible after a stream synchronise; switching this plan to hipStreamSynchronize\n", v);
-                        pollSync = false;
-                    }
-                    return;
-                }
-            }
-            cpuRelax();
+        if (!spinUntil([&] { return __atomic_load_n(stampFlag, __ATOMIC_ACQUIRE) == v; })) {      // polling is given up for this plan rather than the process
+            fprintf(stderr, "Opt(amd): completion stamp %llu not visible after a stream synchronise; switching this plan to hipStreamSynchronize\n", v);
+            pollSync = false;
         }
     }
     // Sum of a host-visible reduction whose producer wrote tagged word pairs: spin on pinned memory until every pair carries `tag`; nothing was put in the
-    // stream for it.  The stream is queried now and then so that a faulted or never-issued producer ends in an error message instead of a hang.
+    // stream for it.  NaN: a pair never arrived.
     double pollTaggedSum(const Reduction& R, unsigned tag) {
         const unsigned long long* w = reinterpret_cast<const unsigned long long*>(R.partials);
-        double s = 0; unsigned long spins = 0; bool synced = false;
+        double s = 0;
         for (int i = 0; i < R.n; ++i) {
             unsigned long long lo, hi;
-            for (;;) {
-                lo = __atomic_load_n(w + 2 * i, __ATOMIC_ACQUIRE); hi = __atomic_load_n(w + 2 * i + 1, __ATOMIC_ACQUIRE);
-                if ((unsigned)(lo >> 32) == tag && (unsigned)(hi >> 32) == tag) break;
-                if ((++spins & 0x3fff) == 0) {
-                    const hipError_t e = hipStreamQuery(stream);
-                    if (e != hipSuccess && e != hipErrorNotReady) HIP_CHECK(e);
-                    if (e == hipSuccess) {      // idle stream, word not seen: one real synchronise and one more look before calling it an error
-                        if (!synced) { HIP_CHECK(hipStreamSynchronize(stream)); synced = true; continue; }
-                        fprintf(stderr, "Opt(amd): Q partial %d of tag %u never arrived (the producing launch was not issued or faulted); this early-out test is skipped and the plan goes back to reading Q through the stream\n", i, tag);
-                        return std::nan("");
-                    }
-                }
-                cpuRelax();
+            if (!spinUntil([&] {
+                    lo = __atomic_load_n(w + 2 * i, __ATOMIC_ACQUIRE); hi = __atomic_load_n(w + 2 * i + 1, __ATOMIC_ACQUIRE);
+                    return (unsigned)(lo >> 32) == tag && (unsigned)(hi >> 32) == tag; })) {
+                fprintf(stderr, "Opt(amd): Q partial %d of tag %u never arrived (the producing launch was not issued or faulted); this early-out test is skipped and the plan goes back to reading Q through the stream\n", i, tag);
+                return std::nan("");
             }
             const unsigned long long bits = (lo & 0xffffffffull) | (hi << 32);
             double v; memcpy(&v, &bits, sizeof v); s += v;
@@ -648,25 +374,25 @@ struct PcgSolver : SolverBase {
         E->evalCost(R, ctx);
         return (T)hostSum(R);
     }
-    void imageOp(int kind) {   // 0: X += delta, 1: prevX = X, 2: X = prevX
+    void costTransition(T newCost) {      // an accepted step's cost as the reference prints it
+        if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)newCost);
+        prevCost = newCost;
+    }
+    enum class ImageOp { update, saveAndUpdate, revert };      // X += delta (PCGLinearUpdate); prevX = X, then X += delta (LM); X = prevX (revertUpdate)
+    void imageOp(ImageOp op) {
         for (size_t i = 0; i < E->unknowns.size(); ++i) {
             const auto& u = E->unknowns[i];
             long cnt = u.elems * u.channels;
             int grid = (int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, 4096));
             T* X = E->unknownPtr((int)i);
-            if (kind == 0) { ScopedKernel k(ctx, "PCGLinearUpdate"); k_axpyImage<T><<<grid, kBlock, 0, stream>>>(X, delta + u.offset, cnt); }
-            else if (kind == 3) { ScopedKernel k(ctx, "PCGLinearUpdate"); k_saveAndUpdate<T><<<grid, kBlock, 0, stream>>>(X, prevX + u.offset, delta + u.offset, cnt); }   // 1 then 0
-            else if (kind == 1) { ScopedKernel k(ctx, "savePreviousUnknowns"); k_copy<T><<<grid, kBlock, 0, stream>>>(prevX + u.offset, X, cnt); }
+            if (op == ImageOp::update) { ScopedKernel k(ctx, "PCGLinearUpdate"); k_axpyImage<T><<<grid, kBlock, 0, stream>>>(X, delta + u.offset, cnt); }
+            else if (op == ImageOp::saveAndUpdate) { ScopedKernel k(ctx, "PCGLinearUpdate"); k_saveAndUpdate<T><<<grid, kBlock, 0, stream>>>(X, prevX + u.offset, delta + u.offset, cnt); }
             else { ScopedKernel k(ctx, "revertUpdate"); k_copy<T><<<grid, kBlock, 0, stream>>>(X, prevX + u.offset, cnt); }
         }
     }
-    void record(int lIter, const Reduction& aDenR, const Reduction& bNumR, double q) {
+    void record(int lIter, const Reduction& aDenR, const Reduction& bNumR, double q) {      // (bNumR in slab mode: forConsumers' all-reduced total)
         if (!traceEnabled) return;
-        double aDen = hostSum(aDenR), bNum = distributed ? 0.0 : hostSum(bNumR), aNum = 0;
-        if (distributed) { HIP_CHECK(hipMemcpyAsync(hostBuf, bNumR.partials, sizeof(double), hipMemcpyDeviceToHost, stream)); HIP_CHECK(hipStreamSynchronize(stream)); bNum = hostBuf[0]; }
-        HIP_CHECK(hipMemcpyAsync(hostBuf, scal + aSlot, sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        aNum = hostBuf[0];
+        const double aDen = hostSum(aDenR), bNum = distributed ? readBack(bNumR.partials, 1)[0] : hostSum(bNumR), aNum = readBack(scal + aSlot, 1)[0];
         trace.insert(trace.end(), {(double)sp.nIter, (double)lIter, aNum, aDen, bNum, q});
     }
 
@@ -681,6 +407,24 @@ struct PcgSolver : SolverBase {
         ScopedKernel k(ctx, "PCGStep2_delta");
         k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, delta, pv, nPacks, aNumTotal, aNum.partials, aNum.n, aDen.partials, aDen.n, pOwed, aOwed);
     }
+    // LM's split residual reset (solver.t:1077-1083): deltaOut = delta (+ the owed term) + alpha pv with alpha as in step2Delta, then r = b - (J^T J + CtC) deltaOut
+    // afresh, z = M r and the partial sums of the beta numerator (redB) and of Q (Q).  deltaOnly: r, z and the sums are dead, the reference's computeAdelta and second
+    // half are not run.  fusible: the kernel set may do those two in one pass (applyJTJResetLM) -- asked on behalf of the launch-per-iteration loop only.
+    void splitResidualReset(T* deltaOut, const T* pv, const T* preArg, const double* aNumTotal, const Reduction& aNum, const Reduction& aDen, Reduction& Q,
+                            bool fusible, bool deltaOnly = false, const T* pOwed = nullptr, const T* aOwed = nullptr) {
+        { ScopedKernel k(ctx, "PCGStep2_1stHalf");
+          k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, deltaOut, pv, nPacks, aNumTotal, aNum.partials, aNum.n, aDen.partials, aDen.n, pOwed, aOwed); }
+        if (deltaOnly) return;
+        exchangeVector(deltaOut);
+        if (fusible && E->applyJTJResetLM(deltaOut, r, b, preArg, z, CtC, redB, Q, ctx)) return;
+        E->applyJTJ(deltaOut, Adelta, CtC, nullptr, ctx);             // computeAdelta (+_Graph)
+        { ScopedKernel k(ctx, "PCGStep2_2ndHalf");
+          k_step2SecondHalf<T><<<streamGrid, kBlock, 0, stream>>>(deltaOut, r, Adelta, b, preArg, z, nPacks, redB.partials, Q.partials); }
+        redB.n = streamGrid; Q.n = streamGrid;
+    }
+    // After the last iteration of a linear solve only delta survives: r, z, the beta numerator and -- unless someone listens for the "breaking" message or the
+    // trace -- Q are dead, so the last PCGStep2, or the last split residual reset, shrinks to its delta += alpha p and LM's fetchQ (solver.t:1098) is not performed.
+    bool onlyDeltaSurvives(int lIter) const { return lIter + 1 >= sp.lIterations && !traceEnabled && (!lm || verbosity == 0); }
     bool qEarlyOut(int k, T Q1, T Q0, T tol) {      // LM's q-based early out after k iterations (solver.t:1093-1102)
         const T zeta = T(k) * (Q1 - Q0) / Q1;
         if (zeta < tol && verbosity > 0) printf("zeta=%.18g, breaking at iteration: %d\n", (double)zeta, k);
@@ -705,8 +449,8 @@ struct PcgSolver : SolverBase {
 
     // Row slabs: the on-chip solve runs on ALL ranks or on none (their kernels wait for each other): every rank says whether it could, the communicator adds it up.
     // (The vote comes before anything is exchanged: the launch-per-iteration loop needs r = 0 on ghost rows.)
-    bool trySlabOnChip(const T* preArg) {
-        if (!allRanksAgree(onChipAllowed() && preArg && sp.lIterations > 0 && !traceEnabled && E->slabOnChipAvailable(sp.lIterations))) return false;
+    Solved trySlabOnChip(const T* preArg) {
+        if (!allRanksAgree(onChipAllowed() && preArg && sp.lIterations > 0 && !traceEnabled && E->slabOnChipAvailable(sp.lIterations))) return {};
         (void)takeLease();      // (agreed collectively: this rank launches whether or not another plan of this process holds the chip)
         exchangeVector(r); exchangeVector(p);      // the kernel reads r_0, p_0 of its halo rows from the ghost rows
         // A rank whose kernel set refuses after the vote (it should not: the vote covers the communicator's capacity and error state) launches nothing; its
@@ -717,7 +461,7 @@ struct PcgSolver : SolverBase {
         E->onChipVerdict(scal + 5, refused, ctx);
         comm.allReduceSum(comm.ctx, scal + 5, 1, (void*)stream);
         E->onChipApply(delta, scal + 5, refused, ctx);
-        usedOnChip = true; unknownsUpdated = true; return true;
+        return {Path::onChip, true};
     }
     // One GPU: the whole linear solve as one persistent launch with the loop state on chip, if the kernel set has one and the problem fits (iw_onchip.h, sfs_onchip.h,
     // stencil_onchip.h).  Gauss-Newton (lmc == nullptr): it ends with PCGLinearUpdate, guarded by the launch's failure word; a traced solve gets its per-iteration
@@ -725,8 +469,8 @@ struct PcgSolver : SolverBase {
     // listening caller (verbosity > 0), the iteration and zeta of the early-out in a pinned word, from which the reference's "breaking at iteration" message is
     // printed once the step has drained (afterLinearSolve; verbose and silent runs take the SAME path).  Not reproduced there: the message of an early-out decided
     // after the LAST iteration (its test is dead -- the loop has ended -- and the on-chip kernels do not form it).
-    bool tryOnChip(const T* preArg, const OnChipLm<T>* lmc) {
-        if (!((preArg || chip) && onChipAllowed() && sp.lIterations > 0 && takeLease())) return false;
+    Solved tryOnChip(const T* preArg, const OnChipLm<T>* lmc) {
+        if (!((preArg || chip) && onChipAllowed() && sp.lIterations > 0 && takeLease())) return {};
         double* tr = nullptr;
         if (traceEnabled) {
             if (onChipTraceCap < sp.lIterations) { if (onChipTrace) HIP_CHECK(hipFree(onChipTrace)); onChipTraceCap = sp.lIterations; HIP_CHECK(hipMalloc((void**)&onChipTrace, sizeof(double) * 4 * onChipTraceCap)); }
@@ -734,19 +478,26 @@ struct PcgSolver : SolverBase {
         }
         OnChipLm<T> la = lmc ? *lmc : OnChipLm<T>{};
         if (lmc) { if (!lmBreak) lmBreak = (double*)allocPinned(64); lmBreak[0] = 0.0; lmBreak[1] = 0.0; la.breakInfo = verbosity > 0 ? lmBreak : nullptr; }
-        if (!E->pcgSolveOnChip(r, p, delta, sp.lIterations, tr, lmc ? &la : nullptr, ctx)) { dropLease(); return false; }
-        usedOnChip = true;
-        if (!lmc) unknownsUpdated = true;
-        if (traceEnabled) {
-            std::vector<double> h(4 * (size_t)sp.lIterations);
-            HIP_CHECK(hipMemcpyAsync(h.data(), onChipTrace, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            for (int k = 0; k < sp.lIterations; ++k) traceRow(k, h[4 * k], h[4 * k + 1], h[4 * k + 2], h[4 * k + 3], false);
+        if (!E->pcgSolveOnChip(r, p, delta, sp.lIterations, tr, lmc ? &la : nullptr, ctx)) { dropLease(); return {}; }
+        constexpr int kRows = 2 * kMaxPartials / 4;      // rows of four that fit hostBuf: one copy for any usual lIterations
+        for (int k0 = 0; traceEnabled && k0 < sp.lIterations; k0 += kRows) {
+            const int rows = std::min(kRows, sp.lIterations - k0);
+            const double* h = readBack(onChipTrace + 4 * k0, 4 * rows);
+            for (int k = 0; k < rows; ++k) traceRow(k0 + k, h[4 * k], h[4 * k + 1], h[4 * k + 2], h[4 * k + 3], false);
         }
-        return true;
+        return {Path::onChip, !lmc};
     }
-    // ---- Gauss-Newton PCG loop as one kernel launch per iteration (energy.h PcgIterArgs); returns false if the energy has no such kernel ----
-    bool runLaunchPerIterationGN(const T* preArg) {
+    // What both launch-per-iteration loops tell a launch: from (r, Ap_X, p) into the alternate buffers, the previous launch's four sums in, this launch's into setS[cur]
+    PcgIterArgs<T> iterArgs(const T* preArg, bool first, const Reduction (&prev)[4], int cur, PcgIterResult<T>* result) {
+        PcgIterArgs<T> a{};
+        a.rOld = r; a.ApOld = Ap_X; a.pOld = p; a.rNew = r2; a.ApNew = Ap2; a.pNew = p2; a.delta = delta; a.pre = preArg; a.first = first;
+        a.aNumPrev = prev[0]; a.aDenPrev = prev[1]; a.s2Prev = prev[2]; a.s3Prev = prev[3];
+        a.aNum = &setS[cur][0]; a.aDen = &setS[cur][1]; a.s2 = &setS[cur][2]; a.s3 = &setS[cur][3];
+        a.result = result;
+        return a;
+    }
+    // ---- Gauss-Newton PCG loop as one kernel launch per iteration (energy.h PcgIterArgs); Path::none if the energy has no such kernel ----
+    Solved runLaunchPerIterationGN(const T* preArg) {
         Reduction prev[4] = {redC, Reduction{}, Reduction{}, Reduction{}};   // alphaNum_0 = sum r.p from PCGInit1
         if (distributed) {   // ghost rows of r_0, M and p_0 (written as 0 by evalJTF / PCGInit1_Finish) come from the slab neighbours once
             exchangeVector(r); exchangeVector(p); if (preArg) exchangeVector(preconditioner);
@@ -756,11 +507,8 @@ struct PcgSolver : SolverBase {
         OptAmd_MailRef mail{nullptr, 0, 0, 0, 0, nullptr};      // where the next launch finds the previous launch's sums if they were posted, not reduced
         const IterTraits traits = E->iterTraits(false);
         for (int lIter = 0; lIter < sp.lIterations; ++lIter) {
-            PcgIterArgs<T> a{};
-            PcgIterResult<T> done; a.result = &done;
-            a.rOld = r; a.ApOld = Ap_X; a.pOld = p; a.rNew = r2; a.ApNew = Ap2; a.pNew = p2; a.delta = delta; a.pre = preArg; a.first = lIter == 0;
-            a.aNumPrev = prev[0]; a.aDenPrev = prev[1]; a.s2Prev = prev[2]; a.s3Prev = prev[3];
-            a.aNum = &setS[cur][0]; a.aDen = &setS[cur][1]; a.s2 = &setS[cur][2]; a.s3 = &setS[cur][3];
+            PcgIterResult<T> done;
+            PcgIterArgs<T> a = iterArgs(preArg, lIter == 0, prev, cur, &done);
             a.mail = mail;
             // the all-reduce of THIS launch's sums, carried out by the launch itself if the communicator can plan it and the kernel set can post
             bool planned = false;
@@ -769,7 +517,7 @@ struct PcgSolver : SolverBase {
                 planned = commExt.allReducePlan(comm.ctx, 4, &a.post, &nextMail) != 0;
             if (distributed && lIter > 0 && !traits.stateExchange) exchangeVector(Ap_X);   // kernel with Ap in memory: r and p ghost rows are kept current by the kernel itself
             deltaTrial.beforeLaunch(*this, lIter); a.delta = delta;
-            if (!E->pcgIteration(a, ctx)) { if (lIter == 0) return false; refusedMidLoop(); }
+            if (!E->pcgIteration(a, ctx)) { if (lIter == 0) return {}; refusedMidLoop(); }
             std::swap(r, r2); std::swap(Ap_X, Ap2); std::swap(p, p2);
             if (distributed && traits.stateExchange && done.exchangeDue) {   // Ap-free kernel: the neighbours' edge rows of r_k and p_k, one grouped exchange
                 std::vector<T*> bases;
@@ -798,27 +546,29 @@ struct PcgSolver : SolverBase {
                     for (int i = 0; i < 4; ++i) { prev[i].partials = tot + i; prev[i].n = 1; }
                 }
             }
-            if (traceEnabled) {      // (four reads in this order)
-                const double aNum = hostSumLocal(prev[0]), aDen = hostSumLocal(prev[1]), s2 = hostSumLocal(prev[2]), s3 = hostSumLocal(prev[3]);
-                traceRow(lIter, aNum, aDen, s2, s3, lIter == 0 && !preArg && !E->usesGraph);
+            if (traceEnabled) {      // (four reads in this order: aNum, aDen, s2, s3 -- all-reduced already in slab mode)
+                double h[4];
+                for (int i = 0; i < 4; ++i) h[i] = sumOf(readBack(prev[i].partials, prev[i].n), prev[i].n);
+                traceRow(lIter, h[0], h[1], h[2], h[3], lIter == 0 && !preArg && !E->usesGraph);
             }
             cur ^= 1;
         }
         // the last iteration's delta += alpha p (PCGStep2, solver.t:461-462); r, z, p of that iteration are dead.  A kernel set may fold it, its own
         // deferred terms and PCGLinearUpdate into one pass over the unknowns (EnergyOps::finishUpdate).
-        if (!distributed && !traceEnabled && sp.lIterations > 0 && E->finishUpdate(delta, prev[0], prev[1], ctx)) { unknownsUpdated = true; return true; }
+        if (!distributed && !traceEnabled && sp.lIterations > 0 && E->finishUpdate(delta, prev[0], prev[1], ctx)) return {Path::perIteration, true};
         const T* pLast = E->pcgFinish(delta, ctx);
         if (!pLast) pLast = p;
         finalizeLocal(prev[0], scal + 2);
         step2Delta(pLast, scal + 2, Reduction{}, prev[1]);
-        return true;
+        return {Path::perIteration, false};
     }
     // ---- the same for Levenberg-Marquardt (energy.h PcgIterArgs, LM fields).  Launch k applies Step2 and Step3 of iteration k-1 and
     // delivers Q_{k-1}, so the q early-out of iteration k-1 (solver.t:1093-1102) is decided after launch k -- by which time the
     // state is exactly the reference's at its break (Step3 runs before fetchQ there too).  Every residual_reset_period-th iteration
     // ends with the reference's split Step2 (delta, A delta, r = b - A delta; :1077-1083) on the generic kernels; the next launch then
-    // restarts from that r with beta given directly.  Returns false (nothing touched) if the energy has no such kernel.
-    bool runLaunchPerIterationLM(const T* preArg) {
+    // restarts from that r with beta given directly.  Path::none (nothing touched) if the energy has no such kernel.
+    Solved runLaunchPerIterationLM(const T* preArg) {
+        const Solved ran{Path::perIteration, false};
         T Q0 = 0;                                                   // (initLinearSystem: Q_0 is 0)
         if (!delta2) delta2 = allocVec();                       // zero-filled like delta; every launch that updates delta rewrites all of it
         Reduction prev[4] = {redC, Reduction{}, Reduction{}, Reduction{}};
@@ -831,19 +581,16 @@ struct PcgSolver : SolverBase {
         auto pNow = [&]() -> const T* { return adopted.p ? adopted.p : p; };      // p of the launch adopted last (a kernel set may keep the directions in buffers of its own)
         // One launch from the current state into the alternate buffers (r2, p2, delta2, setS[cur]); adopted later by pointer swaps.
         auto issue = [&](int k, bool restart) -> bool {
-            PcgIterArgs<T> a{};
-            a.rOld = r; a.ApOld = Ap_X; a.pOld = p; a.rNew = r2; a.ApNew = Ap2; a.pNew = p2; a.delta = delta; a.deltaOut = delta2; a.pre = preArg; a.first = k == 0;
-            a.aNumPrev = prev[0]; a.aDenPrev = prev[1]; a.s2Prev = prev[2]; a.s3Prev = prev[3];
-            a.aNum = &setS[cur][0]; a.aDen = &setS[cur][1]; a.s2 = &setS[cur][2]; a.s3 = &setS[cur][3];
-            a.CtC = CtC; a.b = b; a.q = (k & 1) ? &redQ2 : &redQ; a.afterReset = restart ? 1 : 0; a.betaNum = bNumDirect; a.betaDen = bDenDirect; a.qInit = qDirect;
+            issuedRes = PcgIterResult<T>{};
+            PcgIterArgs<T> a = iterArgs(preArg, k == 0, prev, cur, &issuedRes);
+            a.deltaOut = delta2; a.CtC = CtC; a.b = b; a.q = (k & 1) ? &redQ2 : &redQ; a.afterReset = restart ? 1 : 0; a.betaNum = bNumDirect; a.betaDen = bDenDirect; a.qInit = qDirect;
             if (taggedQ) { if (++launchTag == 0) ++launchTag; a.qTag = tagOf[k & 1] = launchTag; } else tagOf[k & 1] = 0;      // (0: this launch writes plain partials)
             a.lmRadius = trust_region_radius; a.lmMinDiag = min_lm_diagonal; a.lmMaxDiag = max_lm_diagonal;
             issuedRestart = restart;
-            issuedRes = PcgIterResult<T>{}; a.result = &issuedRes;
             return E->pcgIteration(a, ctx);
         };
         for (int lIter = 0; lIter < sp.lIterations; ++lIter) {
-            if (!issued && !issue(lIter, afterReset)) { if (lIter == 0) return false; refusedMidLoop(); }
+            if (!issued && !issue(lIter, afterReset)) { if (lIter == 0) return {}; refusedMidLoop(); }
             issued = false;
             // adopt launch lIter
             const bool appliedStep2 = lIter > 0 && !issuedRestart;    // it finished iteration lIter-1 (delta, r, z, p) and summed Q_{lIter-1}
@@ -855,20 +602,11 @@ struct PcgSolver : SolverBase {
             afterReset = false;
             const bool resetNow = sp.residual_reset_period > 0 && ((lIter + 1) % sp.residual_reset_period) == 0;      // (a period of 0: never -- Lua's x % 0 is nan, solver.t:1077)
             // The split residual reset (solver.t:1077-1083) of this iteration: delta += alpha p, then r = b - (J^T J + CtC) delta afresh.
-            // After the last iteration only delta survives (r, z, the beta numerator and -- unless someone listens for the message -- Q are dead), so the
-            // reference's computeAdelta and second half are not run then.
-            const bool lastAndSilent = lIter + 1 >= sp.lIterations && verbosity == 0;
+            // After the last iteration of a silent solve the reference's computeAdelta and second half are not run (onlyDeltaSurvives).
+            const bool deltaOnly = onlyDeltaSurvives(lIter);
             auto resetKernels = [&](T* deltaOut) {
                 // (a term the adopted launch left owed goes in first, in the same pass; `delta` itself stays as it is: an early-out decided below flushes it there)
-                const T *pOwed = appliedStep2 ? adopted.owedP : nullptr, *aOwed = appliedStep2 ? adopted.owedAlpha : nullptr;
-                { ScopedKernel k(ctx, "PCGStep2_1stHalf");
-                  k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, deltaOut, pNow(), nPacks, nullptr, prev[0].partials, prev[0].n, prev[1].partials, prev[1].n, pOwed, aOwed); }
-                if (lastAndSilent) return;
-                if (E->applyJTJResetLM(deltaOut, r, b, preArg, z, CtC, redB, redQR, ctx)) return;      // computeAdelta + the second half in one pass
-                E->applyJTJ(deltaOut, Adelta, CtC, nullptr, ctx);             // computeAdelta
-                { ScopedKernel k(ctx, "PCGStep2_2ndHalf");
-                  k_step2SecondHalf<T><<<streamGrid, kBlock, 0, stream>>>(deltaOut, r, Adelta, b, preArg, z, nPacks, redB.partials, redQR.partials); }
-                redB.n = streamGrid; redQR.n = streamGrid;
+                splitResidualReset(deltaOut, pNow(), preArg, nullptr, prev[0], prev[1], redQR, true, deltaOnly, appliedStep2 ? adopted.owedP : nullptr, appliedStep2 ? adopted.owedAlpha : nullptr);
             };
             bool resetIssued = false;
             if (appliedStep2) {
@@ -883,7 +621,7 @@ struct PcgSolver : SolverBase {
                 if (Q1 != Q1) {      // a tagged Q partial never arrived (pollTaggedSum said why): this iteration's test is skipped, Q0 stays the last known value, and the
                     taggedQ = false; //  plan reads Q through the stream (beginHostSum / endHostSum) from here on, so the later early-out tests are real again
                 } else {
-                    if (qEarlyOut(lIter, Q1, Q0, (T)sp.q_tolerance)) { if (adopted.owedP) E->addOwedTerm(delta, adopted.owedP, adopted.owedAlpha, ctx); return true; }
+                    if (qEarlyOut(lIter, Q1, Q0, (T)sp.q_tolerance)) { if (adopted.owedP) E->addOwedTerm(delta, adopted.owedP, adopted.owedAlpha, ctx); return ran; }
                     Q0 = Q1;
                 }
             }
@@ -893,10 +631,10 @@ struct PcgSolver : SolverBase {
                 deltaOwed = false;
                 // fetchQ (solver.t:1098).  After the last iteration its only effect is the message below: the loop ends either way, so the blocking
                 // read (one drain of the stream per outer iteration when residual_reset_period == lIterations, the default) happens only when someone is listening.
-                if (!lastAndSilent) {
+                if (!deltaOnly) {
                     qDirect = hostSum(redQR);
                     const T Q1 = (T)qDirect;
-                    if (qEarlyOut(lIter + 1, Q1, Q0, (T)sp.q_tolerance)) return true;
+                    if (qEarlyOut(lIter + 1, Q1, Q0, (T)sp.q_tolerance)) return ran;
                     Q0 = Q1;
                 }
                 afterReset = true; bNumDirect = redB; bDenDirect = prev[0];
@@ -905,13 +643,7 @@ struct PcgSolver : SolverBase {
         if (deltaOwed) {   // the last iteration's delta += alpha p; its r, z, p and Q are dead (the reference's last fetchQ can only break a finished loop)
             step2Delta(pNow(), nullptr, prev[0], prev[1], adopted.owedP, adopted.owedAlpha);      // (... behind the term a deferring last launch left owed)
         }
-        return true;
-    }
-    double hostSumLocal(const Reduction& R) {   // host value of an (already all-reduced, if distributed) reduction
-        HIP_CHECK(hipMemcpyAsync(hostBuf, R.partials, R.n * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        double s = 0; for (int i = 0; i < R.n; ++i) s += hostBuf[i];
-        return s;
+        return ran;
     }
     void finalizeLocal(const Reduction& R, double* dst) { k_finalizeSum<<<1, kBlock, 0, stream>>>(R.partials, R.n, dst); }
 
@@ -932,7 +664,7 @@ struct PcgSolver : SolverBase {
         E->precompute(ctx);
         // (inside Opt_ProblemSolve the first step follows at once on the same unknowns: its PCGInit1 rides on this cost pass where the kernel set can -- see initLinearSystem)
         jtfReady = false; pendingSteps.clear(); if (chip) chip->setStepSlot(-1);
-        if (!lm && !distributed && insideSolve && E->bindInvariantDuringSolve() && sp.nIterations > 0 && singleKernelAllowed() && sp.lIterations > 0 &&
+        if (boundOncePerSolve() && sp.nIterations > 0 && gnInitByKernelSet() &&
             E->evalCostAndJTFInit(redCH, r, p, delta, nPad, redC, ctx)) { jtfReady = true; prevCost = (T)hostSum(redCH); }
         else prevCost = computeCost();
     }
@@ -962,9 +694,7 @@ struct PcgSolver : SolverBase {
         }
         E->patchFinish(ctx);
         E->precompute(ctx);
-        const T newCost = computeCost();
-        if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)newCost);
-        prevCost = newCost;
+        costTransition(computeCost());
         sp.nIter += 1;
         return 1;
     }
@@ -985,9 +715,8 @@ struct PcgSolver : SolverBase {
         int failed = -1;
         for (const PendingStep& ps : pendingSteps) {
             if (ps.onChip && chip->stepFailed(ps.slot)) { failed = ps.step; break; }
-            double c = 0; for (int i = 0; i < costRing[ps.slot].n; ++i) c += costRing[ps.slot].partials[i];
-            if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)(T)c);
-            prevCost = (T)c; lastStepOnChip = ps.onChip;
+            costTransition((T)sumOf(costRing[ps.slot].partials, costRing[ps.slot].n));
+            lastStepOnChip = ps.onChip;
         }
         pendingSteps.clear();
         if (chip) chip->clearStepSlots();
@@ -998,12 +727,13 @@ struct PcgSolver : SolverBase {
     void rewindTo(int f) {
         (void)chip->failedNow();      // (consumes the launch's failure word)
         onChipFailure("the solve goes back to that step");
+        lastStepOnChip = false;
         sp.nIter = f;
     }
     void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipPre = preconditioner; E->graphFused = sp.amd_graph_fused != 0 && sp.amd_reference_order == 0; }      // (EnergyOps::onChipLevel, graphFused)
     int stepOnce(void** params, bool& again) {
         tellOnChipLevel();
-        if (!(insideSolve && boundForSolve && E->bindInvariantDuringSolve())) E->bind(params, ctx);      // (EnergyOps::bindInvariantDuringSolve: once per Opt_ProblemSolve where nothing bind() derives can have changed)
+        if (!boundOncePerSolve()) E->bind(params, ctx);
         const bool mayDefer = !lm && !distributed && insideSolve && !traceEnabled && E->supportsDeferredSteps();
         if (!pendingSteps.empty() && (!mayDefer || sp.nIter >= sp.nIterations)) {      // (cannot happen: the last step of a solve is never deferred -- kept so that no cost is ever lost)
             drain();
@@ -1015,18 +745,17 @@ struct PcgSolver : SolverBase {
         if (chip) chip->setStepSlot(deferSlot);
         const T* preArg = E->usePreconditioner ? preconditioner : nullptr;   // solver.t:467-470: pre = 1 unless the energy preconditions
         const Init init = initLinearSystem();
-        solveLinear(preArg, init, false);
-        AfterSolve a = afterLinearSolve(deferSlot);
+        const Solved solved = solveLinear(preArg, init, false);
+        AfterSolve a = afterLinearSolve(deferSlot, solved);
         if (a.deferred) {      // (the lease stays with this plan until the steps are settled)
-            pendingSteps.push_back({deferSlot, sp.nIter, usedOnChip});
-            usedOnChip = false;
+            pendingSteps.push_back({deferSlot, sp.nIter, solved.onChip()});
             sp.nIter += 1;
             onChipCleanStep();
             return 1;
         }
-        if (!settleAndRedo(preArg, deferSlot, a, again)) return 1;
+        if (!settleAndRedo(preArg, deferSlot, solved, a, again)) return 1;
         if (lm && !lmDecision(a.newCost, a.modelCostChange)) return 0;
-        if (!lm) { if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)a.newCost); prevCost = a.newCost; }
+        if (!lm) costTransition(a.newCost);
         sp.nIter += 1;
         onChipCleanStep();
         return 1;
@@ -1036,11 +765,10 @@ struct PcgSolver : SolverBase {
     // LM's fetchQ behind it (solver.t:1050) is not performed: Q_0 = 1/2 sum delta . (r + b) with the delta PCGInit1 has just zeroed is exactly 0 for every finite r.
     enum class Init { carried, jtfInit, jtfInitLM, generic };      // carried: the previous step's cost pass ran this PCGInit1 (EnergyOps::evalCostAndJTFInit)
     Init initLinearSystem() {
-        unknownsUpdated = false;
         aSlot = 0;
         const bool carried = jtfReady && insideSolve;      // r, p and the partial sums of r.p are already there: the previous step's cost pass wrote them from these very unknowns
         jtfReady = false;
-        if (!lm && !distributed && singleKernelAllowed() && sp.lIterations > 0 && (carried || E->evalJTFInit(r, p, delta, nPad, redC, ctx)))
+        if (gnInitByKernelSet() && (carried || E->evalJTFInit(r, p, delta, nPad, redC, ctx)))
             return carried ? Init::carried : Init::jtfInit;
         if (lm && !distributed) {
             LmInitArgs<T> la{CtC, SSq, r, delta, preconditioner, b, p, trust_region_radius, min_lm_diagonal, max_lm_diagonal, sp.nIter == 0 ? 1 : 0, &redC, &redQ};
@@ -1059,25 +787,26 @@ struct PcgSolver : SolverBase {
     OnChipLm<T> lmControls() const { return OnChipLm<T>{trust_region_radius, min_lm_diagonal, max_lm_diagonal, (T)sp.q_tolerance, sp.residual_reset_period, CtC, sp.amd_onchip}; }
     // The one place that picks the linear solve's path, the first that takes it: (1) on chip -- in slab mode behind the vote every rank issues --, (2) the kernel set's
     // launch-per-iteration loop, (3) the reference-order loop.  (1) and (2) need singleKernelAllowed() (off with OPT_AMD_ONEKERNEL=0 or amd_reference_order=1), in LM
-    // also OPT_AMD_ONEKERNEL_LM, one GPU and no trace.  A redo after an on-chip time-out stops short of (3): false, and the step runs again from its PCGInit1.
-    bool solveLinear(const T* preArg, Init init, bool redo) {
+    // also OPT_AMD_ONEKERNEL_LM, one GPU and no trace.  A redo after an on-chip time-out stops short of (3): Path::none, and the step runs again from its PCGInit1.
+    Solved solveLinear(const T* preArg, Init init, bool redo) {
         if (singleKernelAllowed()) {
+            Solved s;
             if (lm) {
                 const OnChipLm<T> la = lmControls();
-                if (oneKernelLM && !distributed && !traceEnabled && (tryOnChip(preArg, &la) || runLaunchPerIterationLM(preArg))) return true;
+                if (oneKernelLM && !distributed && !traceEnabled && ((s = tryOnChip(preArg, &la)) || (s = runLaunchPerIterationLM(preArg)))) return s;
             } else {
-                if (distributed ? trySlabOnChip(preArg) : tryOnChip(preArg, nullptr)) return true;
-                if ((!distributed || E->iterTraits(false).slabAvailable) && runLaunchPerIterationGN(preArg)) return true;
+                if ((s = distributed ? trySlabOnChip(preArg) : tryOnChip(preArg, nullptr))) return s;
+                if ((!distributed || E->iterTraits(false).slabAvailable) && (s = runLaunchPerIterationGN(preArg))) return s;
             }
         }
-        if (redo) return false;
+        if (redo) return {};
         if (init == Init::carried || init == Init::jtfInit) {      // the kernel set accepted evalJTFInit but refused the loop (it should not): PCGInit1 again -- a library does not exit()
             fprintf(stderr, "Opt(amd): the kernel set accepted evalJTFInit but refused the single-kernel loop; this step runs on the generic kernels\n");
             E->evalJTF(r, CtC, ctx);
             initFinish();
         }
         runReferenceOrderLoop(preArg);
-        return true;
+        return {Path::referenceOrder, false};
     }
     // The reference's loop: PCGStep1, PCGStep2, PCGStep3 per iteration (solver.t:1056-1103).  Step3 of iteration k is fused into Step1 of iteration k+1 when the energy
     // offers that kernel (it only feeds the next Step1; after the last iteration p is dead).  None of Step3 + Step1 touches what survives a q early-out (delta, and p only
@@ -1091,17 +820,9 @@ struct PcgSolver : SolverBase {
         if (sp.lIterations > 0) aDen = stepThreeAndOne(nullptr);     // Step1 of iteration 0
         for (int lIter = 0; lIter < sp.lIterations; ++lIter) {
             const bool reset = lm && sp.residual_reset_period > 0 && ((lIter + 1) % sp.residual_reset_period) == 0;
-            // After the last iteration only delta survives: r, z, the beta numerator and (unless someone listens for the "breaking" message) Q are dead, so the
-            // last PCGStep2 -- or the last split residual reset -- shrinks to its delta += alpha p.
-            if (lIter + 1 >= sp.lIterations && !traceEnabled && (!lm || verbosity == 0)) { step2Delta(p, scal + aSlot, Reduction{}, aDen); break; }
-            if (reset) {   // solver.t:1077-1083
-                { ScopedKernel k(ctx, "PCGStep2_1stHalf"); k_step2FirstHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, delta, p, nPacks, scal + aSlot, nullptr, 0, aDen.partials, aDen.n); }
-                exchangeVector(delta);
-                E->applyJTJ(delta, Adelta, CtC, nullptr, ctx);             // computeAdelta (+_Graph)
-                { ScopedKernel k(ctx, "PCGStep2_2ndHalf");
-                  k_step2SecondHalf<T><<<streamGrid, kBlock, 0, stream>>>(delta, r, Adelta, b, preArg, z, nPacks, redB.partials, redQ.partials); }
-                redB.n = streamGrid; redQ.n = streamGrid;
-            } else {
+            if (onlyDeltaSurvives(lIter)) { step2Delta(p, scal + aSlot, Reduction{}, aDen); break; }
+            if (reset) splitResidualReset(delta, p, preArg, scal + aSlot, Reduction{}, aDen, redQ, false);
+            else {
                 ScopedKernel k(ctx, "PCGStep2");
                 if (lm) k_step2<T, true><<<streamGrid, kBlock, 0, stream>>>(delta, p, r, Ap_X, preArg, b, z, nPacks, scal + aSlot, aDen.partials, aDen.n, redB.partials, redQ.partials);
                 else k_step2<T, false><<<streamGrid, kBlock, 0, stream>>>(delta, p, r, Ap_X, preArg, nullptr, z, nPacks, scal + aSlot, aDen.partials, aDen.n, redB.partials, nullptr);
@@ -1110,9 +831,7 @@ struct PcgSolver : SolverBase {
             bNum = forConsumers(redB, 1);      // (PCGStep3 of this iteration runs with the next PCGStep1)
             const bool more = lIter + 1 < sp.lIterations;
             double qh = 0;
-            const bool deadFetch = lm && !more && verbosity == 0 && !traceEnabled;   // fetchQ after the last iteration only feeds the "breaking" message
-            if (deadFetch) {
-            } else if (lm && speculate) {
+            if (lm && speculate) {
                 beginHostSum(redQ);
                 if (more) aDen = stepThreeAndOne(&bNum);
                 qh = endHostSum();
@@ -1120,7 +839,7 @@ struct PcgSolver : SolverBase {
                 if (lm) qh = hostSum(redQ);
                 if (traceEnabled) record(lIter, aDen, bNum, qh);
             }
-            if (lm && !deadFetch) {   // solver.t:1093-1102
+            if (lm) {   // solver.t:1093-1102
                 const T Q1 = (T)qh;
                 if (qEarlyOut(lIter + 1, Q1, Q0, (T)sp.q_tolerance)) break;
                 Q0 = Q1;
@@ -1149,32 +868,28 @@ struct PcgSolver : SolverBase {
     // model cost, then updates, then reads the new cost (two blocking copies); neither value steers anything before both are known, so all of it is enqueued
     // and the stream is drained once.  deferred: nothing was read back (deferSlot: this step's cost buffer, or -1).
     struct AfterSolve { T newCost = 0, modelCostChange = 0; bool deferred = false; };
-    AfterSolve afterLinearSolve(int deferSlot) {
+    AfterSolve afterLinearSolve(int deferSlot, Solved solved) {
         AfterSolve a;
         if (lm) {   // solver.t:1108-1113, 819-827
             exchangeVector(delta);
             E->evalModelCost(delta, distributed ? redA : redMH, ctx);   // (its own partials buffer: the value is read together with the new cost below)
-            imageOp(3);   // savePreviousUnknowns + PCGLinearUpdate
-        } else if (!unknownsUpdated) imageOp(0);   // PCGLinearUpdate
+            imageOp(ImageOp::saveAndUpdate);
+        } else if (!solved.updated) imageOp(ImageOp::update);
         exchangeUnknowns();
         E->precompute(ctx);
         if (lm && !distributed) {
             E->evalCost(redCH, ctx);                   // both sets of partials are written straight to pinned memory: one drain, no copy kernels
             drain();
-            if (usedOnChip && verbosity > 0 && lmBreak && lmBreak[0] > 0.0 && !chip->failedPeek()) { printf("zeta=%.18g, breaking at iteration: %d\n", lmBreak[1], (int)lmBreak[0] - 1); lmBreak[0] = 0.0; }
-            double sm = 0, sc = 0;
-            for (int i = 0; i < redMH.n; ++i) sm += redMH.partials[i];
-            for (int i = 0; i < redCH.n; ++i) sc += redCH.partials[i];
-            a.newCost = (T)sc;
-            a.modelCostChange = modelCostChange((T)sm);
+            if (solved.onChip() && verbosity > 0 && lmBreak && lmBreak[0] > 0.0 && !chip->failedPeek()) { printf("zeta=%.18g, breaking at iteration: %d\n", lmBreak[1], (int)lmBreak[0] - 1); lmBreak[0] = 0.0; }
+            a.newCost = (T)sumOf(redCH.partials, redCH.n);
+            a.modelCostChange = modelCostChange((T)sumOf(redMH.partials, redMH.n));
             return a;
         }
         if (lm) a.modelCostChange = modelCostChange((T)hostSum(redA));
         // Gauss-Newton inside Opt_ProblemSolve with another step to come: that step's PCGInit1 reads the unknowns this cost reads, and no caller code runs in
         // between -- one pass does both where the kernel set can (same cost bits: same grid, same expressions).  A step on the generic kernels (back-off after
         // an on-chip time-out included) does not ask.
-        const bool carry = !lm && !distributed && insideSolve && boundForSolve && E->bindInvariantDuringSolve() && sp.nIter + 1 < sp.nIterations &&
-                           singleKernelAllowed() && sp.lIterations > 0;
+        const bool carry = boundOncePerSolve() && sp.nIter + 1 < sp.nIterations && gnInitByKernelSet();
         Reduction& costR = deferSlot >= 0 ? costRing[deferSlot] : redCH;
         if (deferSlot >= 0 && !costR.partials) { costR.partials = (double*)allocPinned(2 * kMaxPartials * sizeof(double)); costR.hostVisible = true; }
         if (carry && E->evalCostAndJTFInit(costR, r, p, delta, nPad, redC, ctx)) {
@@ -1185,34 +900,32 @@ struct PcgSolver : SolverBase {
         return a;
     }
     // Behind the cost read: the deferred steps, then this step's on-chip verdict (a time-out redoes the linear solve).  false: the step ends here.
-    bool settleAndRedo(const T* preArg, int deferSlot, AfterSolve& a, bool& again) {
+    bool settleAndRedo(const T* preArg, int deferSlot, Solved solved, AfterSolve& a, bool& again) {
         if (!pendingSteps.empty()) {      // the stream has drained (this step's cost was read): what the deferred steps before it left
-            const bool thisOnChip = usedOnChip;
             const int f = settlePending();
             if (f >= 0) {
                 // from step f on nothing was applied -- unless THIS step ran on the streaming kernels (it cannot while the path is armed; if it did, it was a valid step from
                 // the unknowns of step f and counts as that step)
                 rewindTo(f);
-                if (!thisOnChip) { if (verbosity > 0) printf("cost: %f -> %f\n", (double)prevCost, (double)a.newCost); prevCost = a.newCost; sp.nIter = f + 1; }
+                if (!solved.onChip()) { costTransition(a.newCost); sp.nIter = f + 1; }
                 return false;      // (jtfReady says whether this step's cost pass carried a PCGInit1 for the unknowns as they stand; the last step of a solve carries none)
             }
-            if (!usedOnChip) dropLease();
+            if (!solved.onChip()) dropLease();
         }
-        lastStepOnChip = usedOnChip;
-        if (!usedOnChip) return true;      // (the stream has drained: the cost was read)
-        usedOnChip = false;
-        if (!chip->failedNow()) { dropLease(); return true; }      // the launch has left the chip
+        const bool timedOut = solved.onChip() && chip->failedNow();      // (the stream has drained: the cost was read)
+        lastStepOnChip = solved.onChip() && !timedOut;
+        if (!timedOut) { if (solved.onChip()) dropLease(); return true; }      // the launch has left the chip
         onChipFailure("this linear solve is redone");
-        unknownsUpdated = false;
         if (lm) {      // the kernel produced no delta: the update above added nothing meaningful -- back to the saved unknowns, then the launch-per-iteration loop
-            imageOp(2);
+            imageOp(ImageOp::revert);
             E->precompute(ctx);      // (workgroups that had finished before the others gave up may have written their delta: the update above was then not the identity)
         }
         // Gauss-Newton: nothing was applied (iw_applyDelta checks the flag -- in slab mode the all-reduced verdict, so no rank kept its update).
         // The redone loop starts from delta = 0 as PCGInit1 left it: the ROWS = 16 variant accumulates delta in memory while it runs.
         HIP_CHECK(hipMemsetAsync(delta, 0, nPad * sizeof(T), stream));
-        if (!solveLinear(preArg, Init::generic, true)) { again = true; return false; }      // (no launch-per-iteration loop: the whole step again on the generic kernels)
-        a = afterLinearSolve(deferSlot);
+        const Solved redone = solveLinear(preArg, Init::generic, true);
+        if (!redone) { again = true; return false; }      // (no launch-per-iteration loop: the whole step again on the generic kernels)
+        a = afterLinearSolve(deferSlot, redone);
         return true;
     }
     // LM's accept / reject (solver.t:1119-1157).  false: a tolerance was reached and the solve has ended (cleanup has run).
@@ -1235,7 +948,7 @@ struct PcgSolver : SolverBase {
             radius_decrease_factor = T(2.0);
             prevCost = newCost;
         } else {
-            imageOp(2);   // revertUpdate
+            imageOp(ImageOp::revert);
             trust_region_radius = trust_region_radius / radius_decrease_factor;
             if (verbosity > 0) printf(" trust_region_radius=%f \n", (double)trust_region_radius);
             radius_decrease_factor = T(2.0) * radius_decrease_factor;
@@ -1347,17 +1060,15 @@ bool SolverBase::setParameter(const char* name, const void* value) {   // solver
     return false;
 }
 
-SolverBase* makeSolver(const EnergyInfo& info, bool lm, bool patch, bool doublePrecision, const unsigned* dims, bool timing, int verbosity) {
-    if (doublePrecision && !info.floatOnly) {
-        EnergyOps<double>* e = info.makeDouble(dims);
-        if (!e) return nullptr;
-        if (patch && !e->supportsPatch()) { delete e; return nullptr; }
-        auto* s = new PcgSolver<double>(e, lm, timing, verbosity); s->patch = patch; return s;
-    }
-    EnergyOps<float>* e = info.makeFloat(dims);
+template <class T>
+static SolverBase* makeSolverOf(EnergyOps<T>* e, bool lm, bool patch, bool timing, int verbosity) {
     if (!e) return nullptr;
     if (patch && !e->supportsPatch()) { delete e; return nullptr; }
-    auto* s = new PcgSolver<float>(e, lm, timing, verbosity); s->patch = patch; return s;
+    auto* s = new PcgSolver<T>(e, lm, timing, verbosity); s->patch = patch; return s;
+}
+SolverBase* makeSolver(const EnergyInfo& info, bool lm, bool patch, bool doublePrecision, const unsigned* dims, bool timing, int verbosity) {
+    if (doublePrecision && !info.floatOnly) return makeSolverOf(info.makeDouble(dims), lm, patch, timing, verbosity);
+    return makeSolverOf(info.makeFloat(dims), lm, patch, timing, verbosity);
 }
 
 }  // namespace optamd

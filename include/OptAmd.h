@@ -76,9 +76,10 @@ double OptAmd_PlanTrustRegionRadius(Opt_Plan* plan);
  *   0  launch-per-iteration kernels (the problem does not fit the chip, the kernel set has no on-chip solve, it is switched off: "amd_onchip" = 0 / "amd_reference_order",
  *      or a Levenberg-Marquardt solve passes a residual reset -- lIterations > residual_reset_period -- on a kernel set that keeps such a solve on chip only with
  *      "amd_onchip" = 2 (the 5-point stencils) / 3 (shape_from_shading), or image_warping is given a UrShape that is not the unit pixel lattice and "amd_onchip" is below 4,
- *      or a mesh energy runs below "amd_onchip" = 5 or on a graph its one-workgroup solve does not take);
- *   1  the whole linear solve of the last step ran as one persistent on-chip launch (also an image_warping step with a general UrShape under "amd_onchip" = 4, and an
- *      arap_mesh_deformation / volumetric_mesh_deformation step on a small symmetric graph under "amd_onchip" = 5: one workgroup);
+ *      or a mesh energy runs below "amd_onchip" = 5 (ARAP) / 6 (cotangent, embedded, robust) or on a graph its one-workgroup solve does not take);
+ *   1  the whole linear solve of the last step ran as one persistent on-chip launch (also an image_warping step with a general UrShape under "amd_onchip" = 4, an
+ *      arap_mesh_deformation / volumetric_mesh_deformation step on a small symmetric graph under "amd_onchip" = 5, and a cotangent_mesh_smoothing /
+ *      embedded_mesh_deformation / robust_nonrigid_alignment step on a small mesh under "amd_onchip" = 6: one workgroup);
  *   2  the plan is in its back-off after a failed on-chip launch: the waits of a launch's first phase are bounded by 10 ms (passing them proves the whole grid resident;
  *      a foreign tenant holding CUs makes the launch give up there, before anything has been written), the step was redone by the streaming kernels (reported on stderr the
  *      first three times) and the plan stays on them for 8 (then 16, 32 ... 1024) steps before it tries the chip again.  OptAmd_PlanDescribe carries `onchip_fallbacks` and
@@ -113,6 +114,15 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          (the reference's own meshes: small_armadillo 130 / 386 vertices, head 689).  Any other graph keeps the two launches per PCG iteration, and
  *                          OptAmd_PlanDescribe says why (why_not_on_chip).  The kernel has no grid-wide wait and therefore no time-out path.  Under 0-4 and by default
  *                          the mesh energies keep their bits.  Opt-in for the same reason as 2-4.
+ *                          6: as 5, and the functor mesh energies (cotangent_mesh_smoothing, embedded_mesh_deformation, robust_nonrigid_alignment; graph_engine.h) run
+ *                          the whole linear solve, Gauss-Newton and Levenberg-Marquardt, as one launch of ONE workgroup too (ge_onchipPcg, graph_onchip.h): the
+ *                          hyperedges are evaluated once per PCG iteration into the plan's record buffer, the vertices gather them through the incidence lists, p and
+ *                          delta stay in LDS.  Any vertex degree is served (isolated and tail-only vertices, duplicate hyperedges); the vertex count must be within the
+ *                          offered variants: 1024 vertices for cotangent_mesh_smoothing (the reference's example: head.ply, 689 vertices), 512 for the other two,
+ *                          in float and in double.  It wins on meshes of up to a few hundred vertices and loses beyond (profiles/onchip_graph.md).  It needs gather
+ *                          mode and a preconditioned energy; a plan it refuses takes the loop "amd_graph_fused" selects, and OptAmd_PlanDescribe says why
+ *                          (why_not_on_chip).  No grid-wide wait, no time-out path.  Below 6 these energies keep their bits; ARAP at 6 is ARAP at 5.  Opt-in: the
+ *                          path sums in another order than the four-launch loop and takes beta's numerator by expansion.  Measured: profiles/onchip_graph.md.
  *   "amd_graph_fused"      0 (default): nothing changes.  1: cotangent_mesh_smoothing, embedded_mesh_deformation and robust_nonrigid_alignment (the functor mesh
  *                          energies, graph_engine.h) run TWO launches per PCG iteration, Gauss-Newton and Levenberg-Marquardt, float and double, where by default they run
  *                          the reference's sequence in four (PCGStep3, PCGStep1_Graph, PCGStep1, PCGStep2): ge_flatStep (PCGStep2 + PCGStep3 of the previous iteration,

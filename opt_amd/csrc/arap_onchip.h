@@ -12,7 +12,8 @@
 //           from memory where they are used: a few kilobytes that stay in the CU's cache;
 //   A p     the gather of arap_applyEll over the same planes and ELL out-lists, the same expressions in the same order per vertex: both kernels include
 //           arap_half_edge_pair.inc for the walk's body, and differ only in where a neighbour's p comes from;
-//   sums    formed in double; wave sum (ocWaveSum63), one partial per wave in LDS, every lane adds the partials in wave order: the same bits in every lane, in every run.
+//   sums    formed in double; wave sum (ocWaveSum63), one partial per wave in LDS, every lane adds the partials in wave order (onchip_sync.h ocWorkgroupSum): the same bits in
+//           every lane, in every run.
 // The iterates are those of the two-kernel loop -- its terms of the sums (graph_pcg.h iterTerm), its alpha and beta (ocAlpha, ocBeta: the values of
 // graph_flat_scalars.inc) -- only the order of the sums differs, which is why the path is opt-in.  Two pieces remain COPIES of the streaming kernels' text, not shared
 // with them: the centred part at the end of aoApply (arap_applyEll's, arap_applyFused's) and the per-scalar update of the step (arap_flatStepPlanes'); as functions they
@@ -30,7 +31,7 @@
 namespace optamd {
 namespace {
 
-constexpr int kAoMaxWaves = 8, kAoMaxBlock = kAoMaxWaves * kWave;      // one workgroup of up to 512 threads: 2 waves per SIMD, 256 registers per lane (at 1024 threads and 128 registers every variant spilled)
+constexpr int kAoMaxWaves = kOcWgMaxWaves, kAoMaxBlock = kOcWgMaxBlock;      // one workgroup of up to 512 threads: 2 waves per SIMD, 256 registers per lane (at 1024 threads and 128 registers every variant spilled)
 template <class T> struct alignas(2 * sizeof(T)) AoP2 { T a, b; };
 // lanes keep M in registers where V vertices' r, A p, delta and M fit the 128 registers; else M is re-read where it is used
 template <class T, int V> constexpr bool aoKeepsM() { return V * sizeof(T) <= 8; }
@@ -74,22 +75,6 @@ __device__ __forceinline__ void aoApply(const ArapOcArgs<T>& K, const Q4<T>* __r
     if (LMV) { const V3<T> cO = ldv3(K.CtC, iv), cA = ldv3(K.CtC + 3 * N, iv); q.x += cO.x * pv.x; q.y += cO.y * pv.y; q.z += cO.z * pv.z; qa.x = cA.x * pav.x; qa.y = cA.y * pav.y; qa.z = cA.z * pav.z; }
     if (ok) acc += (double)(dot3(pv, q) + dot3(pav, qa));
     oO = V3<T>{q.x + s0, q.y + s1, q.z + s2}; oA = V3<T>{qa.x + s3, qa.y + s4, qa.z + s5};
-}
-
-// NS sums over the workgroup, the same bits in every lane: wave sums (valid in lane 63), one partial per wave in LDS, every lane adds them in wave order.  red:
-// [NS][kAoMaxWaves] doubles, whose entries beyond the launch's waves are zero for the life of the kernel.  One barrier; the caller passes another barrier before it
-// comes back with the same `red` (the one at the top of the iteration), so the partials are not overwritten before every lane has read them.
-template <int NS>
-__device__ __forceinline__ void aoSum(double (&v)[NS], double* red, int lane, int wave, int nW) {
-#pragma unroll
-    for (int q = 0; q < NS; ++q) { const double s = ocWaveSum63(v[q]); if (lane == kWave - 1) red[q * kAoMaxWaves + wave] = s; }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        double t = 0;
-        for (int w = 0; w < nW; w += 2) { const double2 two = *reinterpret_cast<const double2*>(red + q * kAoMaxWaves + w); t += two.x; t += two.y; }
-        v[q] = t;
-    }
 }
 
 template <class T, int V, bool LMV>
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(kAoMaxBlock) void arap_onchipPcg(ArapOcArgs<T> K) {
             }
         }
         if constexpr (LMV) sums[NS - 1] = accQ;
-        aoSum<NS>(sums, red, lane, wave, nW);
+        ocWorkgroupSum<NS>(sums, red, lane, wave, nW);
         if (K.trace && tid == 0) { K.trace[4 * k] = sums[0]; K.trace[4 * k + 1] = sums[1]; K.trace[4 * k + 2] = sums[2]; K.trace[4 * k + 3] = sums[3]; }
         if constexpr (LMV) {      // the q early-out of iteration k - 1 (solver.t:1093-1102): nothing of iteration k has been applied yet
             if (qPending && ocZetaBreak((T)sums[NS - 1], Q0, k, K.qTolerance, K.lmBreak, k + 1)) break;
@@ -209,7 +194,7 @@ __global__ __launch_bounds__(kAoMaxBlock) void arap_onchipPcg(ArapOcArgs<T> K) {
                         for (int c = 0; c < 6; ++c) { const T zz = mm[c] * rr[c]; two[0] += (double)(zz * rr[c]); two[1] += (double)(T(0.5) * (dd[c] * (rr[c] + bb[c]))); }
                     }
                 }
-                aoSum<2>(two, red2, lane, wave, nW);
+                ocWorkgroupSum<2>(two, red2, lane, wave, nW);
                 if (ocZetaBreak((T)two[1], Q0, k + 1, K.qTolerance, K.lmBreak, k + 2)) break;      // the q test of THIS iteration: the split step delivers Q directly
                 const T bNum = (T)two[0], bDen = (T)sums[0];
                 const T betaR = (bDen > T(0)) ? bNum / bDen : T(0);                                 // PCGStep3's guard (solver.t:544-547)

@@ -5,6 +5,7 @@
 // ulp of 1, i.e. by 4e-4 of a sliver triangle's discriminant of 1.6e-4 -- float stages of cotangent on the raptor mesh were 4e-4 .. 7e-4 from the oracle (plain arithmetic).
 #pragma clang fp contract(off)
 #include "graph_engine.h"
+#include "graph_onchip.h"      // the whole linear solve of a small mesh in one workgroup (amd_onchip = 6)
 
 namespace optamd {
 namespace {
@@ -22,6 +23,9 @@ template <class T, int N> __device__ __forceinline__ Dual<T, N> quotient(const D
 template <class T>
 struct CotangentG {
     static constexpr const char* kName = "CotangentG";
+    static constexpr int kOnChipV[2][2] = {{2, 2}, {2, 2}};      // [float, double][GN, LM]: ge_onchipPcg is offered up to this many vertices per lane (graph_onchip.h)
+    static constexpr int kOnChipSlotsPerPass[2] = {4, 2};        // [float, double]: slots differentiated per evaluation of the hyperedge there (Dual<double, 13> spills)
+    static constexpr int kOnChipLdsVectors[2] = {2, 4};          // [float, double]: p and delta in LDS; 3: r too; 4: and A p (else in registers)
     static constexpr bool kSlotAtRunTime = true;
     static constexpr int NIMG = 1, K = 3, V = 4, RV = 3, RE = 3;
     static constexpr __host__ __device__ int imgOf(int) { return 0; }
@@ -72,6 +76,9 @@ struct CotangentG {
 template <class T>
 struct EmbeddedG {
     static constexpr const char* kName = "EmbeddedG";
+    static constexpr int kOnChipV[2][2] = {{1, 1}, {1, 1}};      // (V = 2 lost to the two-launch loop at 529 and at 1024 vertices, profiles/onchip_graph.md; in double it does not fit LDS either)
+    static constexpr int kOnChipSlotsPerPass[2] = {2, 2};
+    static constexpr int kOnChipLdsVectors[2] = {2, 3};
     static constexpr bool kSlotAtRunTime = false;
     static constexpr int NIMG = 2, K = 12, V = 2, RV = 9, RE = 3;
     static constexpr __host__ __device__ int imgOf(int k) { return k < 3 ? 0 : 1; }
@@ -115,6 +122,9 @@ struct EmbeddedG {
 template <class T>
 struct RobustG {
     static constexpr const char* kName = "RobustG";
+    static constexpr int kOnChipV[2][2] = {{1, 1}, {1, 1}};      // (V = 2 lost to the two-launch loop at 529 and at 1024 vertices, profiles/onchip_graph.md; double LM at V = 2 spills)
+    static constexpr int kOnChipSlotsPerPass[2] = {2, 2};
+    static constexpr int kOnChipLdsVectors[2] = {2, 2};
     static constexpr bool kSlotAtRunTime = true;
     static constexpr int NIMG = 3, K = 7, V = 2, RV = 6, RE = 3;
     static constexpr __host__ __device__ int imgOf(int k) { return k < 3 ? 0 : k < 6 ? 1 : 2; }

@@ -12,11 +12,13 @@
 // grouped, OptGraph.h:64-76; plain atomics for the others).
 // Solver parameter amd_graph_fused = 1: J^T J p as ONE launch that evaluates every record in place (ge_gather: the same bits) and the PCG iteration as two launches
 // (ge_flatStep + ge_gather) through the solver's launch-per-iteration loops, where the default runs the reference's sequence in four.
-// The functor G provides (constexpr / static): NIMG, K, imgOf(k), chOf(k), channels(img), V, RV, RE, edgeDepends(ri, j, k), kName (for OptAmd_PlanDescribe), kSlotAtRunTime (ge_slotDispatch);
+// Solver parameter amd_onchip = 6: on a mesh small enough for one workgroup the WHOLE linear solve is one launch (graph_onchip.h ge_onchipPcg; GraphOps::pcgSolveOnChip).
+// The functor G provides (constexpr / static): NIMG, K, imgOf(k), chOf(k), channels(img), V, RV, RE, edgeDepends(ri, j, k), kName (for OptAmd_PlanDescribe), kSlotAtRunTime (ge_slotDispatch), kOnChipV, kOnChipSlotsPerPass, kOnChipLdsVectors (graph_onchip.h);
 // members N, nE, vidx[V], X[NIMG]; host bindParams(void**), unknownParam(img).
 #pragma once
 #include "stencil_engine.h"
 #include "graph_pcg.h"
+#include "onchip_sync.h"
 #include <hipcub/hipcub.hpp>
 
 namespace optamd {
@@ -326,6 +328,19 @@ __global__ __launch_bounds__(kBlock) void ge_flatStep(long n, T* __restrict__ de
     }
 }
 
+// ---- the whole linear solve in one workgroup (solver parameter amd_onchip = 6): the kernel and its variant list are graph_onchip.h, which the file that defines the
+// functors includes behind this one ----
+template <class T, class G>
+struct GeOcArgs {
+    G g; GOff<G> vo; long nScalars; Incidence inc; T* rec; int recInLds;      // rec: the plan's record buffer (K scalars per (slot, hyperedge) here); recInLds: the records live in LDS behind the vectors instead
+    const T* r0; const T* p0; const T* M; T* delta;
+    int L; double* trace;           // 4 doubles per iteration (alphaNum, alphaDen, s2, s3), or nullptr
+    const T* CtC; T qTolerance; int resetPeriod; double* lmBreak;      // Levenberg-Marquardt
+};
+template <class T, class G> constexpr int geOcLdsVectors() { return G::kOnChipLdsVectors[sizeof(T) == 4 ? 0 : 1]; }      // solver vectors the kernel keeps in LDS: p, delta (2); r too (3); and A p (4)
+struct GeOcVariant { int v; const void *gn, *lm; };      // V vertices per lane; nullptr: not offered
+namespace { template <class T, class G> const std::vector<GeOcVariant>& geOcVariants(); }
+
 template <class T, class G>
 struct GraphOps : EnergyOps<T> {
     G g{};
@@ -337,6 +352,7 @@ struct GraphOps : EnergyOps<T> {
         for (int i = 0; i < G::NIMG; ++i) { vo.o[i] = this->nScalars; this->addUnknown(G::unknownParam(i), g.N, G::channels(i)); }
         int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         if (const char* e = getenv("OPT_AMD_GRAPH_GATHER")) useGather = atoi(e) != 0;
+        if (const char* e = getenv("OPT_AMD_ONCHIP_REC_LDS")) ocRecLds = atoi(e) != 0;
     }
     int vgrid(int lanes = 1) const { return (int)std::max<long>(1, std::min<long>((g.N * lanes + kBlock - 1) / kBlock, kMaxPartials / 2)); }
     // gather mode state: incidence lists (rebuilt when the graph arrays change: pointers, count or an order-independent checksum) and the record buffer
@@ -421,14 +437,95 @@ struct GraphOps : EnergyOps<T> {
             [&](const IterSums<T>& S) { return launchGather(a.pNew, a.ApNew, a.CtC, a.aDen->partials, S, ctx); });
         return true;
     }
-    std::string describe(int, bool lmv, const OnChipLm<T>*) override {      // ("key=value; ..." -- no ';' inside a value)
-        if (!this->graphFused) return "path=launch-per-iteration";
+    // ---- the whole linear solve in ONE workgroup (graph_onchip.h; solver parameter amd_onchip = 6): gather mode, any vertex degree (the incidence lists are CSR), as many
+    // vertices as a variant serves ----
+    OnchipGuard ocGuard;      // the switches (OPT_AMD_ONCHIP = 0) and the failure word of the guarded update -- one this kernel never sets: it has no wait that could time out
+    struct OcOffer { int v = 0; const void* fn = nullptr; };
+    std::vector<OcOffer> ocOffers[2];      // [Gauss-Newton, Levenberg-Marquardt]: the variants this device can hold, smallest first
+    bool ocReady = false;
+    static constexpr size_t kOcLdsPerVertex = geOcLdsVectors<T, G>() * G::K * sizeof(T);      // p and delta (and r)
+    static constexpr size_t kOcLdsBudget = 160 * 1024 - 512;      // dynamic LDS of a launch: the CU's 160 KB less the kernel's static staging of the sums (at most 448 bytes)
+    bool ocRecLds = true;      // the records of an iteration live in LDS where they fit beside the vectors (OPT_AMD_ONCHIP_REC_LDS=0, read per plan: always the plan's buffer; the A/B switch of profiles/onchip_graph.md)
+    // dynamic LDS of a launch on the graph as bound: the vectors, then the records if there is room
+    size_t ocLdsBytes(bool* recInLds) const {
+        const size_t vec = (size_t)g.N * kOcLdsPerVertex, recBytes = (size_t)std::max(1, g.nE) * G::V * G::K * sizeof(T);
+        const bool in = ocRecLds && vec + recBytes <= kOcLdsBudget;
+        if (recInLds) *recInLds = in;
+        return (vec + (in ? recBytes : 0) + 15) / 16 * 16;
+    }
+    void ocInit() {
+        if (ocReady) return;
+        ocReady = true;
+        for (const GeOcVariant& v : geOcVariants<T, G>())
+            for (int m = 0; m < 2; ++m) {
+                const void* fn = m ? v.lm : v.gn;
+                if (!fn) continue;
+                hipFuncAttributes fa{};
+                if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.localSizeBytes != 0) { (void)hipGetLastError(); continue; }      // (no scratch in a kernel that is all latency)
+                if ((size_t)v.v * kOcWgMaxBlock * kOcLdsPerVertex > kOcLdsBudget) continue;      // (a variant whose largest mesh the CU cannot hold is not offered)
+                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOcLdsBudget) != hipSuccess) { (void)hipGetLastError(); continue; }
+                ocOffers[m].push_back({v.v, fn});
+            }
+    }
+    long ocMaxVertices(bool lmv) { ocInit(); return ocOffers[lmv].empty() ? 0 : (long)ocOffers[lmv].back().v * kOcWgMaxBlock; }
+    // THE predicate of the path: nullptr (on chip, *pick = the variant) or why the plan keeps its launch-per-iteration loop.  pcgSolveOnChip and describe() both ask here.
+    const char* ocWhyNot(int L, bool lmv, const OnChipLm<T>* lm, const OcOffer** pick = nullptr) {
+        if (this->onChipLevel < 6) return "amd_onchip=6 was not set";
+        if (ocGuard.whyOff()) return ocGuard.whyOff();
+        if (fusedWhyNot()) return fusedWhyNot();      // scatter mode: no incidence lists, no records
+        if (!this->usePreconditioner || !this->onChipPre) return "no preconditioner vector";
+        if (this->slab.active) return "row slabs";
+        if (L <= 0) return "no PCG iterations";
+        if (lmv && lm && !lm->CtC) return "no LM diagonal";
+        if (g.N < 1) return "no vertices";
+        ocInit();
+        for (const OcOffer& o : ocOffers[lmv])
+            if (g.N <= (long)o.v * kOcWgMaxBlock) { if (pick) *pick = &o; return nullptr; }
+        return "too many vertices";
+    }
+    bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
+        const OcOffer* o = nullptr;
+        if (ocWhyNot(L, lm != nullptr, lm, &o) || (lm && !lm->CtC)) return false;
+        // only the waves the mesh needs: those its vertices fill at V per lane, and as many more (up to 8) as its hyperedges fill in the edge phase
+        const int threads = std::max(1, std::max(divUp(divUp(g.N, o->v), kWave), std::min(kOcWgMaxWaves, divUp(g.nE, kWave)))) * kWave;
+        bool recInLds = false;
+        const size_t lds = ocLdsBytes(&recInLds);
+        GeOcArgs<T, G> K{g, vo, this->nScalars, incidence(), rec, recInLds ? 1 : 0, r0, p0, this->onChipPre, delta, L, traceDev, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0), lm ? lm->resetPeriod : 0,
+                         lm ? lm->breakInfo : nullptr};
+        void* kargs[] = {(void*)&K};
+        ocGuard.allocWords(ctx.stream);
+        {
+            ScopedKernel k(ctx, "PCGSolveOnChip");
+            if (hipLaunchKernel(o->fn, dim3(1), dim3(threads), kargs, lds, ctx.stream) != hipSuccess) { (void)hipGetLastError(); ocGuard.enabled = false; return false; }
+        }
+        if (!lm) ocApplyDeltaToUnknowns(*this, delta, 64, ocGuard, ctx);      // PCGLinearUpdate X += delta, guarded (LM: the solver applies the update itself)
+        ocGuard.launched = true;
+        return true;
+    }
+    OnchipGuard* onChipGuard() override { return &ocGuard; }
+    std::string describe(int L, bool lmv, const OnChipLm<T>* lm) override {      // ("key=value; ..." -- no ';' inside a value)
+        const char* prec = sizeof(T) == 4 ? "float" : "double";
+        char buf[500];
+        std::string ocWhy;      // amd_onchip >= 6 and the plan is refused: why
+        if (this->onChipLevel >= 6) {
+            const OcOffer* o = nullptr;
+            const char* why = ocWhyNot(L, lmv, lm, &o);
+            if (!why) {
+                bool recInLds = false;
+                (void)ocLdsBytes(&recInLds);
+                snprintf(buf, sizeof buf, "path=on-chip; workgroups=1; vertices=%ld; hyperedges=%d; variant=ge_onchipPcg<%s, %s, %d, %s>; records=%s", g.N, g.nE, prec, G::kName, o->v, lmv ? "LM" : "GN",
+                         recInLds ? "LDS" : "memory");
+                return buf;
+            }
+            ocWhy = std::string("; why_not_on_chip=") + why;
+            if (!strcmp(why, "too many vertices")) ocWhy += " (the variants serve up to " + std::to_string(ocMaxVertices(lmv)) + ")";
+        }
+        if (!this->graphFused) return "path=launch-per-iteration" + ocWhy;
         const char* why = fusedWhyNot();
         if (!why && !this->usePreconditioner) why = "no preconditioner";
-        char buf[300];
         if (why) snprintf(buf, sizeof buf, "path=launch-per-iteration; why_not_fused=%s", why);
-        else snprintf(buf, sizeof buf, "path=launch-per-iteration; launches_per_iteration=2; kernels=ge_flatStep+ge_gather<%s, %s, %s>", sizeof(T) == 4 ? "float" : "double", G::kName, lmv ? "LM" : "GN");
-        return buf;
+        else snprintf(buf, sizeof buf, "path=launch-per-iteration; launches_per_iteration=2; kernels=ge_flatStep+ge_gather<%s, %s, %s>", prec, G::kName, lmv ? "LM" : "GN");
+        return buf + ocWhy;
     }
     void applyJTJ(const T* v, T* out, const T* CtC, Reduction* dot, LaunchCtx& ctx) override {
         if (fusedOn()) {      // one launch instead of two, the same bits in `out`

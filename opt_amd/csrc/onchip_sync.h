@@ -146,6 +146,24 @@ __device__ __forceinline__ double ocWaveSum63(double v) {
     return v;
 }
 
+// ---- the one-workgroup kernels (arap_onchip.h, graph_onchip.h): one workgroup of up to 512 threads, 2 waves per SIMD, 256 registers per lane ----
+constexpr int kOcWgMaxWaves = 8, kOcWgMaxBlock = kOcWgMaxWaves * kWave;
+// NS sums over the workgroup, the same bits in every lane: wave sums (valid in lane 63), one partial per wave in LDS, every lane adds them in wave order.  red:
+// [NS][kOcWgMaxWaves] doubles, whose entries beyond the launch's waves are zero for the life of the kernel.  One barrier; the caller passes another barrier before it
+// comes back with the same `red` (the one at the top of the iteration), so the partials are not overwritten before every lane has read them.
+template <int NS>
+__device__ __forceinline__ void ocWorkgroupSum(double (&v)[NS], double* red, int lane, int wave, int nW) {
+#pragma unroll
+    for (int q = 0; q < NS; ++q) { const double s = ocWaveSum63(v[q]); if (lane == kWave - 1) red[q * kOcWgMaxWaves + wave] = s; }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        double t = 0;
+        for (int w = 0; w < nW; w += 2) { const double2 two = *reinterpret_cast<const double2*>(red + q * kOcWgMaxWaves + w); t += two.x; t += two.y; }
+        v[q] = t;
+    }
+}
+
 // one scalar as tagged words: a float is one word, a double two (ocSend); the payload of such words once they carry the tag (ocPayload)
 template <bool SYS = false> __device__ __forceinline__ void ocSend(oc_u64* box, int idx, float v, unsigned tag) { ocStore<SYS>(box + idx, tag, __float_as_uint(v)); }
 template <bool SYS = false> __device__ __forceinline__ void ocSend(oc_u64* box, int idx, double v, unsigned tag) {

@@ -79,7 +79,8 @@ double OptAmd_PlanTrustRegionRadius(Opt_Plan* plan);
  *      or a mesh energy runs below "amd_onchip" = 5 (ARAP) / 6 (cotangent, embedded, robust) or on a graph its one-workgroup solve does not take);
  *   1  the whole linear solve of the last step ran as one persistent on-chip launch (also an image_warping step with a general UrShape under "amd_onchip" = 4, an
  *      arap_mesh_deformation / volumetric_mesh_deformation step on a small symmetric graph under "amd_onchip" = 5, and a cotangent_mesh_smoothing /
- *      embedded_mesh_deformation / robust_nonrigid_alignment step on a small mesh under "amd_onchip" = 6: one workgroup);
+ *      embedded_mesh_deformation / robust_nonrigid_alignment step on a small mesh under "amd_onchip" = 6: one workgroup, or on a partitioned mesh under "amd_onchip" = 7:
+ *      several workgroups, which wait for each other and therefore have the time-out path of value 2);
  *   2  the plan is in its back-off after a failed on-chip launch: the waits of a launch's first phase are bounded by 10 ms (passing them proves the whole grid resident;
  *      a foreign tenant holding CUs makes the launch give up there, before anything has been written), the step was redone by the streaming kernels (reported on stderr the
  *      first three times) and the plan stays on them for 8 (then 16, 32 ... 1024) steps before it tries the chip again.  OptAmd_PlanDescribe carries `onchip_fallbacks` and
@@ -123,6 +124,19 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          mode and a preconditioned energy; a plan it refuses takes the loop "amd_graph_fused" selects, and OptAmd_PlanDescribe says why
  *                          (why_not_on_chip).  No grid-wide wait, no time-out path.  Below 6 these energies keep their bits; ARAP at 6 is ARAP at 5.  Opt-in: the
  *                          path sums in another order than the four-launch loop and takes beta's numerator by expansion.  Measured: profiles/onchip_graph.md.
+ *                          7: as 6, and the functor mesh energies may run the whole linear solve as ONE persistent launch of G > 1 workgroups (ge_onchipPcgGrid,
+ *                          graph_onchip_grid.h): the vertices are partitioned on the host along the mesh's connectivity (graph_partition.h), a workgroup evaluates every
+ *                          hyperedge that touches a vertex it owns and keeps p, delta, r and A p of those hyperedges' vertices in LDS; per PCG iteration the owners post
+ *                          A p of their boundary vertices as tagged words and all workgroups meet in ONE bounded grid-wide sum.  Float and double, one GPU, gather mode,
+ *                          a preconditioned energy.  The workgroup count is "amd_onchip_workgroups"; with one workgroup level 7 launches level 6's kernel (the same
+ *                          bits), levels 0-6 keep their bits and their OptAmd_PlanDescribe text, ARAP at 7 is ARAP at 5.  The launch takes the per-device lease and has
+ *                          the time-out protocol of the other multi-workgroup kernels (OptAmd_PlanOnChipStatus value 2).  A plan it refuses (held vertices do not fit
+ *                          LDS, a part's halo does not fit the ring, partition too entangled, ...) takes the loop "amd_graph_fused" selects and says why.  Opt-in: it
+ *                          sums in yet another order.
+ *   "amd_onchip_workgroups" consulted at "amd_onchip" = 7 only.  0 (default): the plan decides -- 32 workgroups on meshes of 130 to 2000 vertices (cotangent_mesh_smoothing in double: up to
+ *                          689), the range in which that was measured faster than every other setting (profiles/onchip_graph_grid.md: e.g. embedded on the raptor's 2000
+ *                          vertices 11.9 us per PCG iteration against 18.0, cotangent on head.ply 17.1 against 23.9); elsewhere, and where the plan does not fit, what 6 does.  n >= 1: n workgroups, clamped so that
+ *                          every workgroup owns at least one vertex and to the family's cap of 32.  OptAmd_PlanDescribe reports the count used (workgroups=).
  *   "amd_graph_fused"      0 (default): nothing changes.  1: cotangent_mesh_smoothing, embedded_mesh_deformation and robust_nonrigid_alignment (the functor mesh
  *                          energies, graph_engine.h) run TWO launches per PCG iteration, Gauss-Newton and Levenberg-Marquardt, float and double, where by default they run
  *                          the reference's sequence in four (PCGStep3, PCGStep1_Graph, PCGStep1, PCGStep2): ge_flatStep (PCGStep2 + PCGStep3 of the previous iteration,

@@ -187,6 +187,7 @@ struct EnergyOps {
     // The plan's amd_onchip and the solver's Jacobi preconditioner vector, set by the solver before it binds, initialises a linear system or asks describe(): a kernel set whose
     // on-chip solve depends on the level in Gauss-Newton too, or reads the preconditioner from memory (image_warping with a general UrShape, level 4), finds them here
     int onChipLevel = 1;
+    int onChipWorkgroups = 0;      // the plan's amd_onchip_workgroups (consulted at level 7 by the functor mesh energies: 0 = their own choice)
     T* onChipPre = nullptr;
     // The plan's amd_graph_fused, already combined with amd_reference_order == 0 (which wins over every path selection), handed over with onChipLevel: the functor
     // mesh energies (graph_engine.h) then run two launches per PCG iteration and J^T J p without records; every other kernel set ignores it

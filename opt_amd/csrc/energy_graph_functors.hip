@@ -6,6 +6,7 @@
 #pragma clang fp contract(off)
 #include "graph_engine.h"
 #include "graph_onchip.h"      // the whole linear solve of a small mesh in one workgroup (amd_onchip = 6)
+#include "graph_onchip_grid.h" // ... and of a larger one as one persistent launch of several workgroups (amd_onchip = 7)
 
 namespace optamd {
 namespace {
@@ -26,6 +27,7 @@ struct CotangentG {
     static constexpr int kOnChipV[2][2] = {{2, 2}, {2, 2}};      // [float, double][GN, LM]: ge_onchipPcg is offered up to this many vertices per lane (graph_onchip.h)
     static constexpr int kOnChipSlotsPerPass[2] = {4, 2};        // [float, double]: slots differentiated per evaluation of the hyperedge there (Dual<double, 13> spills)
     static constexpr int kOnChipLdsVectors[2] = {2, 4};          // [float, double]: p and delta in LDS; 3: r too; 4: and A p (else in registers)
+    static constexpr long kOnChipGridAutoMaxVertices[2] = {2000, 689};      // [float, double]: up to here amd_onchip = 7 takes 32 workgroups by itself (profiles/onchip_graph_grid.md; double lost on the raptor)
     static constexpr bool kSlotAtRunTime = true;
     static constexpr int NIMG = 1, K = 3, V = 4, RV = 3, RE = 3;
     static constexpr __host__ __device__ int imgOf(int) { return 0; }
@@ -79,6 +81,7 @@ struct EmbeddedG {
     static constexpr int kOnChipV[2][2] = {{1, 1}, {1, 1}};      // (V = 2 lost to the two-launch loop at 529 and at 1024 vertices, profiles/onchip_graph.md; in double it does not fit LDS either)
     static constexpr int kOnChipSlotsPerPass[2] = {2, 2};
     static constexpr int kOnChipLdsVectors[2] = {2, 3};
+    static constexpr long kOnChipGridAutoMaxVertices[2] = {2000, 2000};
     static constexpr bool kSlotAtRunTime = false;
     static constexpr int NIMG = 2, K = 12, V = 2, RV = 9, RE = 3;
     static constexpr __host__ __device__ int imgOf(int k) { return k < 3 ? 0 : 1; }
@@ -125,6 +128,7 @@ struct RobustG {
     static constexpr int kOnChipV[2][2] = {{1, 1}, {1, 1}};      // (V = 2 lost to the two-launch loop at 529 and at 1024 vertices, profiles/onchip_graph.md; double LM at V = 2 spills)
     static constexpr int kOnChipSlotsPerPass[2] = {2, 2};
     static constexpr int kOnChipLdsVectors[2] = {2, 2};
+    static constexpr long kOnChipGridAutoMaxVertices[2] = {2000, 2000};
     static constexpr bool kSlotAtRunTime = true;
     static constexpr int NIMG = 3, K = 7, V = 2, RV = 6, RE = 3;
     static constexpr __host__ __device__ int imgOf(int k) { return k < 3 ? 0 : k < 6 ? 1 : 2; }

@@ -13,12 +13,14 @@
 // Solver parameter amd_graph_fused = 1: J^T J p as ONE launch that evaluates every record in place (ge_gather: the same bits) and the PCG iteration as two launches
 // (ge_flatStep + ge_gather) through the solver's launch-per-iteration loops, where the default runs the reference's sequence in four.
 // Solver parameter amd_onchip = 6: on a mesh small enough for one workgroup the WHOLE linear solve is one launch (graph_onchip.h ge_onchipPcg; GraphOps::pcgSolveOnChip).
+// Solver parameter amd_onchip = 7: ... or one persistent launch of several workgroups over a partition of the mesh (graph_onchip_grid.h ge_onchipPcgGrid; GraphOps::gg*).
 // The functor G provides (constexpr / static): NIMG, K, imgOf(k), chOf(k), channels(img), V, RV, RE, edgeDepends(ri, j, k), kName (for OptAmd_PlanDescribe), kSlotAtRunTime (ge_slotDispatch), kOnChipV, kOnChipSlotsPerPass, kOnChipLdsVectors (graph_onchip.h);
 // members N, nE, vidx[V], X[NIMG]; host bindParams(void**), unknownParam(img).
 #pragma once
 #include "stencil_engine.h"
 #include "graph_pcg.h"
 #include "onchip_sync.h"
+#include "graph_partition.h"
 #include <hipcub/hipcub.hpp>
 
 namespace optamd {
@@ -341,6 +343,28 @@ template <class T, class G> constexpr int geOcLdsVectors() { return G::kOnChipLd
 struct GeOcVariant { int v; const void *gn, *lm; };      // V vertices per lane; nullptr: not offered
 namespace { template <class T, class G> const std::vector<GeOcVariant>& geOcVariants(); }
 
+// ---- the whole linear solve as one persistent launch of several workgroups (solver parameter amd_onchip = 7): the kernel is graph_onchip_grid.h ----
+constexpr int kGeGridMaxG = 32;       // workgroup cap of the family
+constexpr int kGeGridSumG = 64;       // ocGridSum's MAXG: it adds the workgroups' words a wave (64) at a time
+constexpr int kGeGridRing = 4;        // halo scalars a lane collects per phase: a workgroup's halo is at most kGeGridRing * 512 scalars
+struct GeGridPart {                   // one workgroup's part (graph_partition.h GraphPart), its lists as offsets into GeGridArgs::lists
+    int nOwn, nHeld, nE, nRecv;       // owned / held vertices, hyperedges evaluated, halo scalars collected per phase
+    int oHeld, oEdge, oSlot, oIncOff, oIncIdx, oWire;
+    int oGidx;                        // [nHeld K]: the solver-vector index of every held scalar, bit 31 set on the halo
+    int oRecv;                        // [nRecv][2]: {box index, held scalar} of every halo scalar
+    long recBase;                     // the workgroup's slab of the record buffer, in records
+};
+template <class T, class G>
+struct GeGridArgs {
+    GeOcArgs<T, G> k;                 // what ge_onchipPcg is told, for the whole graph (inc unused; recInLds: every workgroup's records fit behind its vectors)
+    int nG; const GeGridPart* parts; const int* lists;
+    oc_u64 *slots, *box; long boxWords;      // [2][kGeGridSumG][2 NS] words of the sums, [2][boxWords] words of the wires
+    unsigned tag0; int* bad; long long firstTicks, laterTicks; int failAt;
+    int* hostErr;                     // LM: the pinned word a workgroup that gave up raises; Gauss-Newton: nullptr (ocApplyDelta tells the host)
+};
+struct GeGridKernels { const void *gn, *lm; };
+namespace { template <class T, class G> GeGridKernels geGridKernels(); }
+
 template <class T, class G>
 struct GraphOps : EnergyOps<T> {
     G g{};
@@ -360,7 +384,7 @@ struct GraphOps : EnergyOps<T> {
     int *incOff = nullptr, *incIdx = nullptr, *cursors = nullptr; T* rec = nullptr; long recCapacity = 0;
     void* scanTemp = nullptr; size_t scanTempBytes = 0; unsigned long long* dChecksum = nullptr;
     const int* incV[G::V] = {}; int incNE = -1; unsigned long long incSum = 0; bool incValid = false;
-    ~GraphOps() override { for (void* q : {(void*)incOff, (void*)incIdx, (void*)cursors, (void*)rec, scanTemp, (void*)dChecksum}) if (q) (void)hipFree(q); }
+    ~GraphOps() override { for (void* q : {(void*)incOff, (void*)incIdx, (void*)cursors, (void*)rec, scanTemp, (void*)dChecksum, (void*)ggParts, (void*)ggLists, (void*)ggRec}) if (q) (void)hipFree(q); }
     Incidence incidence() const { return useGather ? Incidence{incOff, incIdx} : Incidence{nullptr, nullptr}; }
     void ensureIncidence(LaunchCtx& ctx) {
         hipStream_t st = ctx.stream;
@@ -389,6 +413,7 @@ struct GraphOps : EnergyOps<T> {
         inc_sort<G::V><<<vgrid(), kBlock, 0, st>>>(g.N, incOff, incIdx);
         for (int j = 0; j < G::V; ++j) incV[j] = g.vidx[j];
         incNE = g.nE; incSum = sum; incValid = true;
+        ggBuiltG = 0;      // (the partition of amd_onchip = 7 follows the incidence lists)
     }
     void bind(void** p, LaunchCtx& ctx) override {
         g.bindParams(p);
@@ -439,7 +464,7 @@ struct GraphOps : EnergyOps<T> {
     }
     // ---- the whole linear solve in ONE workgroup (graph_onchip.h; solver parameter amd_onchip = 6): gather mode, any vertex degree (the incidence lists are CSR), as many
     // vertices as a variant serves ----
-    OnchipGuard ocGuard;      // the switches (OPT_AMD_ONCHIP = 0) and the failure word of the guarded update -- one this kernel never sets: it has no wait that could time out
+    OnchipGuard ocGuard;      // the switches (OPT_AMD_ONCHIP = 0) and the failure word of the guarded update -- one ge_onchipPcg never sets (it has no wait that could time out) and ge_onchipPcgGrid does
     struct OcOffer { int v = 0; const void* fn = nullptr; };
     std::vector<OcOffer> ocOffers[2];      // [Gauss-Newton, Levenberg-Marquardt]: the variants this device can hold, smallest first
     bool ocReady = false;
@@ -469,7 +494,8 @@ struct GraphOps : EnergyOps<T> {
     }
     long ocMaxVertices(bool lmv) { ocInit(); return ocOffers[lmv].empty() ? 0 : (long)ocOffers[lmv].back().v * kOcWgMaxBlock; }
     // THE predicate of the path: nullptr (on chip, *pick = the variant) or why the plan keeps its launch-per-iteration loop.  pcgSolveOnChip and describe() both ask here.
-    const char* ocWhyNot(int L, bool lmv, const OnChipLm<T>* lm, const OcOffer** pick = nullptr) {
+    // (what any on-chip solve of the family needs, one workgroup or several)
+    const char* ocCommonWhyNot(int L, bool lmv, const OnChipLm<T>* lm) const {
         if (this->onChipLevel < 6) return "amd_onchip=6 was not set";
         if (ocGuard.whyOff()) return ocGuard.whyOff();
         if (fusedWhyNot()) return fusedWhyNot();      // scatter mode: no incidence lists, no records
@@ -478,12 +504,141 @@ struct GraphOps : EnergyOps<T> {
         if (L <= 0) return "no PCG iterations";
         if (lmv && lm && !lm->CtC) return "no LM diagonal";
         if (g.N < 1) return "no vertices";
+        return nullptr;
+    }
+    const char* ocWhyNot(int L, bool lmv, const OnChipLm<T>* lm, const OcOffer** pick = nullptr) {
+        if (const char* why = ocCommonWhyNot(L, lmv, lm)) return why;
         ocInit();
         for (const OcOffer& o : ocOffers[lmv])
             if (g.N <= (long)o.v * kOcWgMaxBlock) { if (pick) *pick = &o; return nullptr; }
         return "too many vertices";
     }
+    // ---- ... or as ONE persistent launch of several workgroups (graph_onchip_grid.h; solver parameter amd_onchip = 7, amd_onchip_workgroups) ----
+    GraphPartition ggPart;            // the partition in force (host copy: describe() reports from it)
+    int ggBuiltG = 0;                 // its workgroup count; 0: none (the graph has changed: ensureIncidence)
+    GeGridPart* ggParts = nullptr; int* ggLists = nullptr; size_t ggListCap = 0;
+    T* ggRec = nullptr; long ggRecCap = 0;      // the workgroups' record slabs (K scalars per evaluated (hyperedge, slot)), used where the records do not fit LDS
+    oc_u64 *ggSlots = nullptr, *ggBox = nullptr; long ggBoxWords = 0, ggBoxCap = 0;
+    const void* ggFn[2] = {nullptr, nullptr}; bool ggReady = false;
+    static constexpr size_t kGgLdsPerVertex = 4 * G::K * sizeof(T);      // p, delta, r, A p
+    static constexpr size_t kGgLdsBudget = 160 * 1024 - 4096;            // dynamic LDS of a launch: the CU's 160 KB less the kernel's static staging of the sums (OcSumLds for 64 workgroups: at most 2928 bytes)
+    // Automatic workgroup count (amd_onchip_workgroups = 0): the rule of profiles/onchip_graph_grid.md, which names a workload only where the several-workgroup launch
+    // was MEASURED faster than every other setting (median below the minimum of the best of them).  Measured there: 130 .. 2000 vertices, 768 .. 12108 hyperedges, and at
+    // every size the full 32 workgroups were the fastest count.  So: 32 workgroups from kGgAutoMinVertices up to the functor's G::kOnChipGridAutoMaxVertices[precision]
+    // (2000, the largest mesh measured; cotangent in double: 689 -- it lost on the raptor), one workgroup (level 6's behaviour) elsewhere.  A plan the several-workgroup
+    // predicate refuses under the automatic choice (LDS, ring, entanglement) does what level 6 does as well.
+    static constexpr long kGgAutoMinVertices = 130;
+    int ggAutoWorkgroups() const { return g.N >= kGgAutoMinVertices && g.N <= G::kOnChipGridAutoMaxVertices[sizeof(T) == 4 ? 0 : 1] ? kGeGridMaxG : 1; }
+    bool ggForced() const { return this->onChipWorkgroups > 0; }
+    // the workgroup count level 7 asks for on the graph as bound (1: the one-workgroup path)
+    int ggWanted() const {
+        if (this->onChipLevel < 7 || g.N < 1) return 1;
+        return graphPartitionClamp(g.N, this->onChipWorkgroups > 0 ? this->onChipWorkgroups : ggAutoWorkgroups(), kGeGridMaxG);
+    }
+    void ggInit() {
+        if (ggReady) return;
+        ggReady = true;
+        const GeGridKernels ks = geGridKernels<T, G>();
+        for (int m = 0; m < 2; ++m) {
+            const void* fn = m ? ks.lm : ks.gn;
+            hipFuncAttributes fa{};
+            if (!fn || hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.localSizeBytes != 0) { (void)hipGetLastError(); continue; }      // (no scratch in a kernel that is all latency)
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGgLdsBudget) != hipSuccess) { (void)hipGetLastError(); continue; }
+            ggFn[m] = fn;
+        }
+    }
+    // the partition for G workgroups on the graph as bound, on the device (blocking copies: once per graph and workgroup count)
+    void ggEnsure(int G_) {
+        if (ggBuiltG == G_) return;
+        std::vector<int> h[G::V]; const int* hp[G::V];
+        for (int j = 0; j < G::V; ++j) {
+            h[j].resize((size_t)std::max(1, g.nE));
+            if (g.nE > 0) HIP_CHECK(hipMemcpy(h[j].data(), g.vidx[j], (size_t)g.nE * sizeof(int), hipMemcpyDeviceToHost));
+            hp[j] = h[j].data();
+        }
+        ggPart = buildGraphPartition(g.N, g.nE, G::V, hp, G_);
+        std::vector<int> lists; std::vector<GeGridPart> parts((size_t)G_);
+        auto put = [&](const std::vector<int>& v) { const int o = (int)lists.size(); lists.insert(lists.end(), v.begin(), v.end()); return o; };
+        long recBase = 0;
+        for (int w = 0; w < G_; ++w) {
+            const GraphPart& Q = ggPart.parts[(size_t)w]; GeGridPart& D = parts[(size_t)w];
+            const int nHeld = (int)Q.held.size(), nHalo = nHeld - Q.nOwn;
+            D.nOwn = Q.nOwn; D.nHeld = nHeld; D.nE = (int)Q.edge.size(); D.nRecv = nHalo * G::K; D.recBase = recBase;
+            recBase += (long)D.nE * G::V;
+            D.oHeld = put(Q.held); D.oEdge = put(Q.edge); D.oSlot = put(Q.slot); D.oIncOff = put(Q.incOff); D.oIncIdx = put(Q.incIdx); D.oWire = put(Q.wire);
+            GOff<G> lo; { long o = 0; for (int i = 0; i < G::NIMG; ++i) { lo.o[i] = o; o += (long)nHeld * G::channels(i); } }
+            std::vector<int> gidx((size_t)nHeld * G::K), recv((size_t)nHalo * G::K * 2);
+            for (int l = 0; l < nHeld; ++l)
+                for (int k = 0; k < G::K; ++k) {
+                    const long ul = lo.o[G::imgOf(k)] + (long)l * G::channels(G::imgOf(k)) + G::chOf(k), ug = vo.o[G::imgOf(k)] + (long)Q.held[(size_t)l] * G::channels(G::imgOf(k)) + G::chOf(k);
+                    gidx[(size_t)ul] = (int)ug | (l < Q.nOwn ? 0 : (int)0x80000000);
+                    if (l >= Q.nOwn) { const size_t hh = (size_t)(l - Q.nOwn) * G::K + k; recv[2 * hh] = Q.haloWire[(size_t)(l - Q.nOwn)] * G::K + k; recv[2 * hh + 1] = (int)ul; }
+                }
+            D.oGidx = put(gidx); D.oRecv = put(recv);
+        }
+        lists.push_back(0);      // (never empty)
+        HIP_CHECK(hipDeviceSynchronize());      // (no launch still reads the lists about to be replaced)
+        if (lists.size() > ggListCap) { if (ggLists) HIP_CHECK(hipFree(ggLists)); ggListCap = lists.size(); HIP_CHECK(hipMalloc((void**)&ggLists, ggListCap * sizeof(int))); }
+        if (!ggParts) HIP_CHECK(hipMalloc((void**)&ggParts, kGeGridMaxG * sizeof(GeGridPart)));
+        if (recBase > ggRecCap) { if (ggRec) HIP_CHECK(hipFree(ggRec)); ggRecCap = recBase; HIP_CHECK(hipMalloc((void**)&ggRec, (size_t)ggRecCap * G::K * sizeof(T))); }
+        HIP_CHECK(hipMemcpy(ggLists, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ggParts, parts.data(), parts.size() * sizeof(GeGridPart), hipMemcpyHostToDevice));
+        // the tagged words, allocated once per plan: the sums' slots, and the wires' box at its worst case -- every unknown on a wire (a fresh buffer starts cleared: zero is no tag)
+        if (!ggSlots) { const size_t b = sizeof(oc_u64) * 2 * kGeGridSumG * 2 * 5; ggSlots = ocGuard.template allocTagged<oc_u64>(b); HIP_CHECK(hipMemset(ggSlots, 0, b)); }
+        ggBoxWords = std::max<long>(1, (long)ggPart.nWires * G::K * (long)(sizeof(T) / 4));
+        if (!ggBox) { ggBoxCap = std::max<long>(1, this->nScalars * (long)(sizeof(T) / 4)); const size_t b = sizeof(oc_u64) * 2 * (size_t)ggBoxCap; ggBox = ocGuard.template allocTagged<oc_u64>(b); HIP_CHECK(hipMemset(ggBox, 0, b)); }
+        ggBuiltG = G_;
+    }
+    // dynamic LDS of a launch on the partition in force: the vectors of the largest part, then the records of the largest part if there is room
+    size_t ggLdsBytes(bool* recInLds) const {
+        const size_t vec = (size_t)ggPart.heldMax * kGgLdsPerVertex, recBytes = (size_t)std::max(1, ggPart.edgesMax) * G::V * G::K * sizeof(T);
+        const bool in = ocRecLds && vec + recBytes <= kGgLdsBudget;
+        if (recInLds) *recInLds = in;
+        return (vec + (in ? recBytes : 0) + 15) / 16 * 16;
+    }
+    // Redundant evaluation the AUTOMATIC choice allows, as evaluated / total hyperedges: 11 / 4.  The largest ratio measured is 2.68 (cotangent, 130 vertices on 32
+    // workgroups: still faster than every other setting, profiles/onchip_graph_grid.md); beyond what was measured the automatic choice does not go.  A caller who
+    // forces a workgroup count is not held to it.
+    static constexpr long kGgEntangledNum = 11, kGgEntangledDen = 4;
+    // THE predicate of the several-workgroup path: nullptr (on chip with G_ workgroups, the partition built) or why not.  pcgSolveOnChip and describe() both ask here.
+    const char* ggWhyNot(int L, bool lmv, const OnChipLm<T>* lm, int G_) {
+        if (const char* why = ocCommonWhyNot(L, lmv, lm)) return why;
+        if (!incValid) return "no graph bound yet";
+        if (this->nScalars > 0x7fffffffL / 2) return "too many unknowns";
+        ggInit();
+        if (!ggFn[lmv]) return "the kernel is not offered on this device (scratch)";
+        ggEnsure(G_);
+        if ((size_t)ggPart.heldMax * kGgLdsPerVertex > kGgLdsBudget) return "held vertices do not fit LDS";
+        if ((long)ggPart.haloMax * G::K > (long)kGeGridRing * kOcWgMaxBlock) return "a part's halo does not fit the ring";
+        if (!ggForced() && kGgEntangledDen * ggPart.evaluated > kGgEntangledNum * (long)std::max(1, g.nE)) return "partition too entangled";
+        return nullptr;
+    }
+    bool ggSolve(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, int G_, LaunchCtx& ctx) {
+        if (ggWhyNot(L, lm != nullptr, lm, G_) || (lm && !lm->CtC)) return false;
+        bool recInLds = false;
+        const size_t lds = ggLdsBytes(&recInLds);
+        ocGuard.allocWords(ctx.stream);
+        const int period = lm ? lm->resetPeriod : 0, phases = L + (period > 0 ? (L - 1) / period : 0);
+        const OcTimeouts tmo = ocGuard.timeouts(phases, false);
+        GeGridArgs<T, G> A{};
+        A.k = GeOcArgs<T, G>{g, vo, this->nScalars, incidence(), ggRec, recInLds ? 1 : 0, r0, p0, this->onChipPre, delta, L, traceDev, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0), period,
+                             lm ? lm->breakInfo : nullptr};
+        A.nG = G_; A.parts = ggParts; A.lists = ggLists; A.slots = ggSlots; A.box = ggBox; A.boxWords = ggBoxWords;
+        A.tag0 = ocGuard.tags((unsigned)phases, ctx.stream); A.bad = ocGuard.bad; A.firstTicks = tmo.first; A.laterTicks = tmo.later; A.failAt = ocGuard.failAtThisLaunch();
+        A.hostErr = lm ? ocGuard.hostErr : nullptr;
+        void* kargs[] = {(void*)&A};
+        {
+            ScopedKernel k(ctx, "PCGSolveOnChip");
+            if (hipLaunchKernel(ggFn[lm ? 1 : 0], dim3(G_), dim3(kOcWgMaxBlock), kargs, lds, ctx.stream) != hipSuccess) { (void)hipGetLastError(); ocGuard.enabled = false; return false; }
+        }
+        if (!lm) ocApplyDeltaToUnknowns(*this, delta, 64, ocGuard, ctx);      // PCGLinearUpdate X += delta, guarded (LM: the solver applies the update itself)
+        ocGuard.launched = true;
+        return true;
+    }
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
+        if (const int G_ = ggWanted(); G_ > 1) {
+            if (ggForced() || !ggWhyNot(L, lm != nullptr, lm, G_)) return ggSolve(r0, p0, delta, L, traceDev, lm, G_, ctx);
+        }      // (the automatic choice refused: what level 6 does)
         const OcOffer* o = nullptr;
         if (ocWhyNot(L, lm != nullptr, lm, &o) || (lm && !lm->CtC)) return false;
         // only the waves the mesh needs: those its vertices fill at V per lane, and as many more (up to 8) as its hyperedges fill in the edge phase
@@ -503,11 +658,25 @@ struct GraphOps : EnergyOps<T> {
         return true;
     }
     OnchipGuard* onChipGuard() override { return &ocGuard; }
-    std::string describe(int L, bool lmv, const OnChipLm<T>* lm) override {      // ("key=value; ..." -- no ';' inside a value)
+    // ("key=value; ..." -- no ';' inside a value.)  At level 7 with more than one workgroup asked for, the answer needs the partition: the first call for a graph and
+    // workgroup count builds it here (ggEnsure: a device synchronisation and blocking copies of the index arrays), exactly as the first solve would.
+    std::string describe(int L, bool lmv, const OnChipLm<T>* lm) override {
         const char* prec = sizeof(T) == 4 ? "float" : "double";
         char buf[500];
         std::string ocWhy;      // amd_onchip >= 6 and the plan is refused: why
-        if (this->onChipLevel >= 6) {
+        const int G_ = ggWanted();
+        const char* ggWhy = G_ > 1 ? ggWhyNot(L, lmv, lm, G_) : nullptr;
+        if (G_ > 1 && (ggForced() || !ggWhy)) {      // amd_onchip = 7 and more than one workgroup: forced, or chosen and taken (a refused automatic choice does what level 6 does)
+            const char* why = ggWhy;
+            if (!why) {
+                bool recInLds = false;
+                (void)ggLdsBytes(&recInLds);
+                snprintf(buf, sizeof buf, "path=on-chip; workgroups=%d; vertices=%ld; hyperedges=%d; evaluated_hyperedges=%ld; held_vertices_max=%d; variant=ge_onchipPcgGrid<%s, %s, %s>; records=%s", G_, g.N,
+                         g.nE, ggPart.evaluated, ggPart.heldMax, prec, G::kName, lmv ? "LM" : "GN", recInLds ? "LDS" : "memory");
+                return buf;
+            }
+            ocWhy = std::string("; why_not_on_chip=") + why + " (workgroups=" + std::to_string(G_) + ")";
+        } else if (this->onChipLevel >= 6) {
             const OcOffer* o = nullptr;
             const char* why = ocWhyNot(L, lmv, lm, &o);
             if (!why) {

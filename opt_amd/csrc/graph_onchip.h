@@ -28,6 +28,31 @@
 namespace optamd {
 namespace {
 
+// Which vertices and hyperedges a workgroup works on.  GeOcWhole (ge_onchipPcg): the whole graph -- `vec` (p or delta in LDS) is laid out like the solver's vectors, the
+// hyperedges and incidence lists are the graph's own.  GeOcPart (ge_onchipPcgGrid, graph_onchip_grid.h): one part of a partition (graph_partition.h) -- K.g.nE and K.inc
+// are the part's, `vec` holds the part's held vertices under local indices, and what the functor reads from memory keeps its global ids.
+struct GeOcWhole { static constexpr bool kPart = false; };
+template <class G> struct GeOcPart {
+    static constexpr bool kPart = true;
+    GOff<G> vo;                  // offsets of the unknown images in the part's vectors
+    const int* edge;             // global id of the part's hyperedges
+    const int* slot[G::V];       // local vertex index of every slot of them
+    int nOwn;                    // local indices below this are owned: |J p|^2 of a hyperedge is counted where its slot-0 vertex is
+};
+template <class T, class G> __device__ __forceinline__ const GOff<G>& geOcVecOffsets(const GeOcArgs<T, G>& K, const GeOcWhole&) { return K.vo; }
+template <class T, class G> __device__ __forceinline__ const GOff<G>& geOcVecOffsets(const GeOcArgs<T, G>&, const GeOcPart<G>& loc) { return loc.vo; }
+// unknown k of one vertex whose direction sits at index `at` of vec: VertexCtx<T, G, true, true> with the two indices apart
+template <class T, class G>
+struct GeOcPartVertexCtx {
+    typedef Dual<T, 1 + G::K> S;
+    const G& g; long v, at; const T* vec; const GOff<G>& vo;
+    __device__ __forceinline__ S operator()(int k) const {
+        S r(g.X[G::imgOf(k)][v * G::channels(G::imgOf(k)) + G::chOf(k)]);
+        r.d[0] = vec[unknownIndex<T, G>(vo, at, k)]; r.d[1 + k] = T(1);
+        return r;
+    }
+};
+
 // How many slots of a hyperedge one evaluation of G::edgeResiduals differentiates: all V -- EdgeCtx's dual, one evaluation per hyperedge and iteration -- unless the functor
 // names fewer for a precision (G::kOnChipSlotsPerPass[double]): cotangent's Dual<double, 13> alone takes 216 registers, with the loop state it spilled.  Fewer slots per
 // pass mean V / slots evaluations with a shorter dual; forward-mode components do not interact, so the records carry the same bits either way.
@@ -40,6 +65,18 @@ struct GeOcGroupCtx {
     __device__ __forceinline__ S operator()(int j, int k) const {
         S r(g.X[G::imgOf(k)][vid[j] * G::channels(G::imgOf(k)) + G::chOf(k)]);
         r.d[0] = vec[unknownIndex<T, G>(vo, vid[j], k)];
+        if (j >= J0 && j < J0 + NJ) r.d[1 + (j - J0) * G::K + k] = T(1);
+        return r;
+    }
+};
+// ... in a part: the direction of vertex j sits at its local index at[j] of vec (offsets vo: the part's)
+template <class T, class G, int J0, int NJ>
+struct GeOcPartGroupCtx {
+    typedef Dual<T, 1 + NJ * G::K> S;
+    const G& g; long vid[G::V]; long at[G::V]; const T* vec; const GOff<G>& vo;
+    __device__ __forceinline__ S operator()(int j, int k) const {
+        S r(g.X[G::imgOf(k)][vid[j] * G::channels(G::imgOf(k)) + G::chOf(k)]);
+        r.d[0] = vec[unknownIndex<T, G>(vo, at[j], k)];
         if (j >= J0 && j < J0 + NJ) r.d[1 + (j - J0) * G::K + k] = T(1);
         return r;
     }
@@ -62,32 +99,48 @@ __device__ __forceinline__ void geOcStoreRecords(const GeOcArgs<T, G>& K, T* rec
         }
     }
 }
-template <class T, class G, bool JP2, int J0>
-__device__ __forceinline__ void geOcSlotGroups(const GeOcArgs<T, G>& K, T* rec, const T* vec, const long (&vid)[G::V], long e, bool ok, double& acc) {
+// (Two bodies, one per view: written as one body over a context type -- or with one context whose index array equals vid[] in the whole-graph view -- the four double
+// cotangent ge_onchipPcg kernels allocate other registers (224 .. 248 VGPRs where the build before had 244 .. 256), and their resources are frozen by
+// tests/test_onchip_graph_grid_resources.py.  In a part: e is where the records go, eg the hyperedge the functor evaluates, at the local indices of its vertices, cnt whether this workgroup counts its |J vec|^2)
+template <class T, class G, bool JP2, int J0, class Loc = GeOcWhole>
+__device__ __forceinline__ void geOcSlotGroups(const GeOcArgs<T, G>& K, T* rec, const T* vec, const long (&vid)[G::V], long e, bool ok, double& acc, const Loc& loc = Loc(),
+                                               const long* at = nullptr, long eg = 0, bool cnt = false) {
     constexpr int NJ = geOcSlotsPerPass<T, G>();
     static_assert(G::V % NJ == 0, "the slots of a hyperedge divide into whole passes");
-    typedef GeOcGroupCtx<T, G, J0, NJ> Ctx;
-    typedef typename Ctx::S S;
-    Ctx X{K.g, {}, vec, K.vo};
+    if constexpr (Loc::kPart) {
+        typedef GeOcPartGroupCtx<T, G, J0, NJ> Ctx;
+        typedef typename Ctx::S S;
+        Ctx X{K.g, {}, {}, vec, loc.vo};
 #pragma unroll
-    for (int j = 0; j < G::V; ++j) X.vid[j] = vid[j];
-    S r[G::RE];
-    K.g.template edgeResiduals<S>(X, e, r);
-    if (JP2 && J0 == 0 && ok) { T s = 0; for (int i = 0; i < G::RE; ++i) s += r[i].d[0] * r[i].d[0]; acc += (double)s; }
-    geOcStoreRecords<T, G, J0, NJ>(K, rec, r, e, ok);
-    if constexpr (J0 + NJ < G::V) geOcSlotGroups<T, G, JP2, J0 + NJ>(K, rec, vec, vid, e, ok, acc);
+        for (int j = 0; j < G::V; ++j) { X.vid[j] = vid[j]; X.at[j] = at[j]; }
+        S r[G::RE];
+        K.g.template edgeResiduals<S>(X, eg, r);
+        if (JP2 && J0 == 0 && cnt) { T s = 0; for (int i = 0; i < G::RE; ++i) s += r[i].d[0] * r[i].d[0]; acc += (double)s; }
+        geOcStoreRecords<T, G, J0, NJ>(K, rec, r, e, ok);
+    } else {
+        typedef GeOcGroupCtx<T, G, J0, NJ> Ctx;
+        typedef typename Ctx::S S;
+        Ctx X{K.g, {}, vec, K.vo};
+#pragma unroll
+        for (int j = 0; j < G::V; ++j) X.vid[j] = vid[j];
+        S r[G::RE];
+        K.g.template edgeResiduals<S>(X, e, r);
+        if (JP2 && J0 == 0 && ok) { T s = 0; for (int i = 0; i < G::RE; ++i) s += r[i].d[0] * r[i].d[0]; acc += (double)s; }
+        geOcStoreRecords<T, G, J0, NJ>(K, rec, r, e, ok);
+    }
+    if constexpr (J0 + NJ < G::V) geOcSlotGroups<T, G, JP2, J0 + NJ>(K, rec, vec, vid, e, ok, acc, loc, at, eg, cnt);
 }
 
 // J^T J vec of every hyperedge as records, rec[(slot * nE + e) * K + k]: ge_edges<T, G, 3> in gather mode, with vec in LDS.  JP2: acc += |J vec|^2, the hyperedges' share
 // of vec . A vec (counted once per hyperedge).  Called by every thread of the workgroup.
-template <class T, class G, bool JP2>
-__device__ __forceinline__ void geOcEdges(const GeOcArgs<T, G>& K, T* rec, const T* vec, int tid, int nT, double& acc) {
+template <class T, class G, bool JP2, class Loc = GeOcWhole>
+__device__ __forceinline__ void geOcEdges(const GeOcArgs<T, G>& K, T* rec, const T* vec, int tid, int nT, double& acc, const Loc& loc = Loc()) {
     const G& g = K.g;
     const int nE = g.nE, nLoop = (nE + nT - 1) / nT * nT;
     for (int e0 = tid; e0 < nLoop; e0 += nT) {
         const bool ok = e0 < nE;
         const long e = ok ? e0 : 0;
-        if constexpr (geOcSlotsPerPass<T, G>() == G::V) {
+        if constexpr (!Loc::kPart && geOcSlotsPerPass<T, G>() == G::V) {
             typedef EdgeCtx<T, G, true, true> Ctx;
             typedef typename Ctx::S S;
             Ctx X{g, {}, vec, K.vo};
@@ -99,34 +152,46 @@ __device__ __forceinline__ void geOcEdges(const GeOcArgs<T, G>& K, T* rec, const
             geOcStoreRecords<T, G, 0, G::V>(K, rec, r, e, ok);
         } else {
             long vid[G::V];
+            if constexpr (Loc::kPart) {
+                const long eg = loc.edge[e];
+                long at[G::V];
 #pragma unroll
-            for (int j = 0; j < G::V; ++j) vid[j] = g.vidx[j][e];
-            geOcSlotGroups<T, G, JP2, 0>(K, rec, vec, vid, e, ok, acc);
+                for (int j = 0; j < G::V; ++j) { vid[j] = g.vidx[j][eg]; at[j] = loc.slot[j][e]; }
+                geOcSlotGroups<T, G, JP2, 0>(K, rec, vec, vid, e, ok, acc, loc, at, eg, ok && at[0] < loc.nOwn);
+            } else {
+#pragma unroll
+                for (int j = 0; j < G::V; ++j) vid[j] = g.vidx[j][e];
+                geOcSlotGroups<T, G, JP2, 0>(K, rec, vec, vid, e, ok, acc);
+            }
         }
     }
 }
 
 // (J^T J vec)(v) [+ CtC vec] of vertex v: its own residuals' part, then the records of its (hyperedge, slot) pairs in ascending order, four loads in flight.
-// acc += vec(v) . (own part).  A lane without a vertex (ok == false) evaluates vertex 0 and adds nothing.
-template <class T, class G, bool LMV>
-__device__ __forceinline__ void geOcVertex(const GeOcArgs<T, G>& K, const T* rec, const T* vec, long v, bool ok, T (&gs)[G::K], double& acc) {
+// acc += vec(v) . (own part).  A lane without a vertex (ok == false) evaluates vertex 0 and adds nothing.  In a part (GeOcPart) v is the vertex's global id and `at` its
+// local index: the position of its direction in vec and of its list in K.inc.
+template <class T, class G, bool LMV, class Loc = GeOcWhole>
+__device__ __forceinline__ void geOcVertex(const GeOcArgs<T, G>& K, const T* rec, const T* vec, long v, bool ok, T (&gs)[G::K], double& acc, const Loc& loc = Loc(), long at = 0) {
     constexpr int BATCH = 4;
     const long vv = ok ? v : 0;
+    const long va = Loc::kPart ? (ok ? at : 0) : vv;
+    const GOff<G>& vvo = geOcVecOffsets<T, G>(K, loc);
     typedef VertexCtx<T, G, true, true> Ctx;
     typedef typename Ctx::S S;
     S r[G::RV > 0 ? G::RV : 1];
-    K.g.template vertexResiduals<S>(Ctx{K.g, vv, vec, K.vo}, vv, r);
+    if constexpr (Loc::kPart) K.g.template vertexResiduals<S>(GeOcPartVertexCtx<T, G>{K.g, vv, va, vec, vvo}, vv, r);
+    else K.g.template vertexResiduals<S>(Ctx{K.g, vv, vec, K.vo}, vv, r);
 #pragma unroll
     for (int k = 0; k < G::K; ++k) {
         T gk = 0;
 #pragma unroll
         for (int i = 0; i < G::RV; ++i) gk += r[i].d[1 + k] * r[i].d[0];
-        const long u = unknownIndex<T, G>(K.vo, vv, k);
-        if (LMV) gk += K.CtC[u] * vec[u];
-        if (ok) acc += (double)(vec[u] * gk);
+        const long u = unknownIndex<T, G>(K.vo, vv, k), uv = unknownIndex<T, G>(vvo, va, k);
+        if (LMV) gk += K.CtC[u] * vec[uv];
+        if (ok) acc += (double)(vec[uv] * gk);
         gs[k] = gk;
     }
-    const int tb = ok ? K.inc.off[vv] : 0, te = ok ? K.inc.off[vv + 1] : 0;
+    const int tb = ok ? K.inc.off[va] : 0, te = ok ? K.inc.off[va + 1] : 0;
     for (int t0 = tb; t0 < te; t0 += BATCH) {
         int id[BATCH]; T q[BATCH][G::K];
 #pragma unroll

@@ -730,7 +730,7 @@ struct PcgSolver : SolverBase {
         lastStepOnChip = false;
         sp.nIter = f;
     }
-    void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipPre = preconditioner; E->graphFused = sp.amd_graph_fused != 0 && sp.amd_reference_order == 0; }      // (EnergyOps::onChipLevel, graphFused)
+    void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipWorkgroups = sp.amd_onchip_workgroups; E->onChipPre = preconditioner; E->graphFused = sp.amd_graph_fused != 0 && sp.amd_reference_order == 0; }      // (EnergyOps::onChipLevel, graphFused)
     int stepOnce(void** params, bool& again) {
         tellOnChipLevel();
         if (!boundOncePerSolve()) E->bind(params, ctx);
@@ -1054,7 +1054,7 @@ bool SolverBase::setParameter(const char* name, const void* value) {   // solver
     PF(min_relative_decrease) PF(min_trust_region_radius) PF(max_trust_region_radius) PF(q_tolerance) PF(function_tolerance)
     PF(trust_region_radius) PF(radius_decrease_factor) PF(min_lm_diagonal) PF(max_lm_diagonal)
     PI(residual_reset_period) PI(nIter) PI(nIterations) PI(lIterations) PI(patchIterations) PI(patchSize)
-    PI(amd_reference_order) PI(amd_onchip) PI(amd_graph_fused)
+    PI(amd_reference_order) PI(amd_onchip) PI(amd_onchip_workgroups) PI(amd_graph_fused)
 #undef PF
 #undef PI
     return false;

@@ -6,10 +6,12 @@
 //             to its neighbours' inboxes as tagged words and waits for its own inbox
 //   both   -- one of each per round, the shape of an on-chip iteration
 // Every wait is bounded (wall clock): a protocol error ends the run with a message instead of hanging the GPU.
-//   hipcc --offload-arch=gfx950 -O3 -o /tmp/gridsync tools/microbench_gridsync.hip && /tmp/gridsync [rounds]
+//   hipcc --offload-arch=gfx950 -O3 -o /tmp/gridsync tools/microbench_gridsync.hip && /tmp/gridsync [rounds [workgroups]]
+// With a workgroup count other than 256 only the flat sum runs: the grid-wide wait of a few workgroups in isolation (profiles/onchip_graph_grid.md: 2 .. 32).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <vector>
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
@@ -145,16 +147,17 @@ int main(int argc, char** argv) {
     const int rounds = argc > 1 ? atoi(argv[1]) : 2000;
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
-    const int G = 256, tilesX = 16, tilesY = 16;
+    const int G = argc > 2 ? std::min(256, std::max(1, atoi(argv[2]))) : 256, tilesX = 16, tilesY = 16;
+    const int nModes = G == 256 ? 5 : 1;      // (the tree and the halo are laid out for 16 x 16 workgroups)
     printf("%s, %d CUs; %d workgroups of %d threads, %d rounds per launch\n", prop.name, prop.multiProcessorCount, G, BLOCK, rounds);
     Sync S{};
     S.G = G; S.tilesX = tilesX; S.tilesY = tilesY;
     CHECK(hipMalloc(&S.slots, sizeof(u64) * 2 * G * NW));
-    CHECK(hipMalloc(&S.groupSlots, sizeof(u64) * 2 * (G / 16) * NW));
+    CHECK(hipMalloc(&S.groupSlots, sizeof(u64) * 2 * (G / 16 + 1) * NW));
     CHECK(hipMalloc(&S.inbox, sizeof(u64) * 2 * G * 4 * kSideWords));
     CHECK(hipMalloc(&S.bad, sizeof(int)));
     CHECK(hipMemset(S.slots, 0, sizeof(u64) * 2 * G * NW));
-    CHECK(hipMemset(S.groupSlots, 0, sizeof(u64) * 2 * (G / 16) * NW));
+    CHECK(hipMemset(S.groupSlots, 0, sizeof(u64) * 2 * (G / 16 + 1) * NW));
     CHECK(hipMemset(S.inbox, 0, sizeof(u64) * 2 * G * 4 * kSideWords));
     CHECK(hipMemset(S.bad, 0, sizeof(int)));
     double* out;
@@ -166,7 +169,7 @@ int main(int argc, char** argv) {
     unsigned tag = 1;
     const double expect = 4.0 * G * (G + 1) / 2;     // total of k = 3: sum over g of (g + 1) * 4
     for (int rep = 0; rep < 2; ++rep)
-        for (int mode = 0; mode < 5; ++mode) {
+        for (int mode = 0; mode < nModes; ++mode) {
             CHECK(hipEventRecord(e0));
             switch (mode) {
                 case 0: k_rounds<0><<<G, BLOCK, ldsBytes>>>(S, rounds, tag, out); break;

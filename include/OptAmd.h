@@ -37,6 +37,17 @@ int OptAmd_CheckProblemFile(const char* filename, char* message, int messageLen)
  * edited Energy / Exclude body is refused instead of silently solved as the unedited energy).  0 if the file cannot be read. */
 unsigned long OptAmd_ProblemFileHash(const char* filename);
 
+/* Adds the energies of a plug-in library to the kernel registry (OptAmdPlugin.h says how one is written; opt_amd/build.py build_plugin compiles it;
+ * INTEGRATION.md, "Adding an energy without rebuilding libOpt.so").  Afterwards its .t file is planned, probed and solved through the unmodified API like a
+ * built-in one: by file stem, or by body hash under any file name; an edited body is refused like a built-in energy's.
+ * Returns the number of energies registered (>= 1), or -1 with the reason in `message`.  A refusal leaves the registry as it was, for ALL energies of the
+ * library: a file that cannot be loaded, one without the entry symbol, a plug-in compiled against another layout of the kernel-set interface (its ABI stamp
+ * differs -- checked before anything else of the plug-in runs), an energy that records no body hash, an energy whose name is registered already (so the same
+ * library cannot be loaded twice).  Host-only: needs no GPU.  Thread-safe.  A loaded plug-in stays loaded until the process ends.
+ * The environment variable OPT_AMD_ENERGY_PLUGINS (paths separated by ':') is loaded once, by the first Opt_NewState of the process, so that a caller
+ * written for the reference needs no source change; a path that is refused is reported on stderr and the state is created all the same. */
+int OptAmd_LoadEnergyPlugin(const char* path, char* message, int messageLen);
+
 /* Length of the solver's unknown vector: unknown images in declaration order, each AoS, concatenated
  * (the reference's UnknownType iteration order, API/src/o.t:675-687). */
 long OptAmd_PlanNumUnknownScalars(Opt_Plan* plan);

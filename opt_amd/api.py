@@ -23,7 +23,7 @@ OPT_SYMBOLS = ["Opt_NewState", "Opt_ProblemDefine", "Opt_ProblemDelete", "Opt_Pr
 OPTAMD_SYMBOLS = ["OptAmd_Version", "OptAmd_EnergyCount", "OptAmd_EnergyName", "OptAmd_PlanNumUnknownScalars", "OptAmd_PlanVector",
                   "OptAmd_EvalJTF", "OptAmd_ApplyJTJ", "OptAmd_EvalCost", "OptAmd_PlanEnableTrace", "OptAmd_PlanTraceRows",
                   "OptAmd_PlanGetTrace", "OptAmd_PlanTrustRegionRadius", "OptAmd_PlanKernelTiming", "OptAmd_PlanSetTiming", "OptAmd_PlanKernelCount",
-                  "OptAmd_PlanKernelName", "OptAmd_PlanOnChipStatus", "OptAmd_PlanDescribe", "OptAmd_PlanSetSlab", "OptAmd_PlanSetSlabExt", "OptAmd_CheckProblemFile", "OptAmd_ProblemFileHash",
+                  "OptAmd_PlanKernelName", "OptAmd_PlanOnChipStatus", "OptAmd_PlanDescribe", "OptAmd_PlanSetSlab", "OptAmd_PlanSetSlabExt", "OptAmd_CheckProblemFile", "OptAmd_ProblemFileHash", "OptAmd_LoadEnergyPlugin",
                   "OptAmd_MeasureCopyBandwidth", "OptAmd_DebugOccupy"]
 
 
@@ -91,8 +91,25 @@ def lib():
     L.OptAmd_MeasureCopyBandwidth.restype = cd; L.OptAmd_MeasureCopyBandwidth.argtypes = [cl, ci, ci]
     L.OptAmd_DebugOccupy.restype = ci; L.OptAmd_DebugOccupy.argtypes = [ci, cd, vp]
     L.OptAmd_CheckProblemFile.restype = ci; L.OptAmd_CheckProblemFile.argtypes = [cp, cp, ci]
+    L.OptAmd_ProblemFileHash.restype = ctypes.c_ulong; L.OptAmd_ProblemFileHash.argtypes = [cp]
+    L.OptAmd_LoadEnergyPlugin.restype = ci; L.OptAmd_LoadEnergyPlugin.argtypes = [cp, cp, ci]
     _lib = L
     return L
+
+
+def load_energy_plugin(path):
+    """Register the energies of a plug-in library (include/OptAmdPlugin.h; built by opt_amd.build.build_plugin) for the rest of the process; returns how
+    many it brought.  Raises RuntimeError with the library's message if the plug-in is refused -- the registry is then unchanged.  Host-only."""
+    buf = ctypes.create_string_buffer(1024)
+    n = lib().OptAmd_LoadEnergyPlugin(os.fsencode(path), buf, 1024)
+    if n < 0:
+        raise RuntimeError(buf.value.decode())
+    return n
+
+
+def problem_file_hash(path):
+    """Body hash of a .t file (OptAmd_ProblemFileHash): what a plug-in records in EnergyInfo::bodyHashes.  0 if the file cannot be read."""
+    return lib().OptAmd_ProblemFileHash(os.fsencode(path))
 
 
 def check_problem_file(path):
@@ -131,7 +148,8 @@ class ParamPack:
 
 
 class Solver:
-    """One Opt state + problem + plan, like the reference harness's OptSolver (examples/shared/OptSolver.h:40-97)."""
+    """One Opt state + problem + plan, like the reference harness's OptSolver (examples/shared/OptSolver.h:40-97).
+    `filename` is the path of any .t file the registry serves: energy_file(stem) for a shipped energy, or the .t of an energy a loaded plug-in brought."""
 
     def __init__(self, filename, kind, dims, double=False, verbosity=0, timing=False):
         L = lib()
@@ -139,7 +157,7 @@ class Solver:
         self.state = L.Opt_NewState(ip)
         if not self.state:
             raise RuntimeError("Opt_NewState failed (no HIP device?)")
-        self.problem = L.Opt_ProblemDefine(self.state, filename.encode(), kind.encode())
+        self.problem = L.Opt_ProblemDefine(self.state, os.fsencode(filename), kind.encode())
         d = (ctypes.c_uint * len(dims))(*[int(x) for x in dims])
         self.plan = L.Opt_ProblemPlan(self.state, self.problem, d)
         if not self.plan:

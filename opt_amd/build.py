@@ -22,11 +22,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 REMARKS = ["-Rpass-analysis=kernel-resource-usage"]
 
 
-def kernel_resources():
-    """{demangled kernel name: {"vgprs", "agprs", "scratch", "occupancy", "lds", "sgprs", "file"}} of every kernel of libOpt.so, from the remarks of the last build."""
+def kernel_resources(pattern=None):
+    """{demangled kernel name: {"vgprs", "agprs", "scratch", "occupancy", "lds", "sgprs", "file"}} of every kernel of libOpt.so, from the remarks of the last build
+    (pattern: of the remarks files it names instead -- plugin_kernel_resources)."""
     import re
     out = {}
-    for path in sorted(glob.glob(os.path.join(OBJDIR, "*.remarks"))):
+    for path in sorted(glob.glob(pattern or os.path.join(OBJDIR, "*.remarks"))):
         txt = open(path, errors="replace").read()
         rows = [m.groups() for m in re.finditer(r"Function Name: (\S+).*?SGPRs: (\d+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", txt, re.S)]
         if not rows:
@@ -97,7 +98,54 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
     build_comm(force=force, verbose=verbose)
     build_examples(force=force, verbose=verbose)
+    build_plugin(SAMPLE_PLUGIN, force=force, verbose=verbose)
     return LIB
+
+
+# ---- energy plug-ins (include/OptAmdPlugin.h): one .hip source -> one shared object that libOpt.so loads at run time --------------------------------------------
+PLUGIN_LIBDIR = os.path.join(LIBDIR, "plugins")
+PLUGIN_OBJDIR = os.path.join(HERE, "build_plugins")      # NOT build/: kernel_resources() reads every *.remarks there as libOpt.so's
+SAMPLE_PLUGIN = os.path.join(HERE, "..", "examples", "plugins", "spring_mesh_deformation.hip")
+
+
+def plugin_path(stem):
+    return os.path.join(PLUGIN_LIBDIR, f"lib{stem}.so")
+
+
+def build_plugin(src, out=None, verbose=False, force=True, defines=()):
+    """Compile one plug-in source with the library's flags into opt_amd/lib/plugins/lib<stem>.so (or `out`) and return that path.  The object and its
+    kernel-resource remarks go to opt_amd/build_plugins/ (plugin_kernel_resources reads them).  The plug-in is self-contained: it is not linked against
+    libOpt.so, and -Bsymbolic keeps its own copies of the engine's kernels bound to itself whatever else the process has loaded.
+    force=False: only if the source, a header or the library's own sources' headers are newer than the output.  defines: extra -D (tests)."""
+    src = os.path.abspath(src)
+    stem = os.path.splitext(os.path.basename(src))[0]
+    out = os.path.abspath(out) if out else plugin_path(stem)
+    tag = stem if out == plugin_path(stem) else os.path.splitext(os.path.basename(out))[0]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    os.makedirs(PLUGIN_OBJDIR, exist_ok=True)
+    obj = os.path.join(PLUGIN_OBJDIR, tag + ".o")
+    rem = obj + ".remarks"
+    if not force and os.path.exists(out) and os.path.exists(rem) and os.path.getmtime(out) >= max(os.path.getmtime(src), _deps_mtime()):
+        return out
+    cmd = [HIPCC] + FLAGS + REMARKS + ["-D" + d for d in defines] + ["-I" + CSRC, "-I" + os.path.join(HERE, "..", "include"), "-x", "hip", "-c", src, "-o", obj]
+    if verbose:
+        print(" ".join(cmd))
+    with open(rem, "w") as f:
+        rc = subprocess.call(cmd, stderr=f)
+    if rc != 0:
+        sys.stderr.write("".join(l for l in open(rem, errors="replace") if "remark:" not in l))
+        os.remove(rem)
+        raise RuntimeError("hipcc failed for: " + src)
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-o", out, obj]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return out
+
+
+def plugin_kernel_resources(stem):
+    """kernel_resources() of the plug-in built from <stem>.hip."""
+    return kernel_resources(os.path.join(PLUGIN_OBJDIR, stem + ".o.remarks"))
 
 
 EXAMPLES_DIR = os.path.join(HERE, "..", "examples")

@@ -6,6 +6,7 @@
 // kernels so it can pick its own tiling, LDS staging and reduction shape.
 #pragma once
 #include "common.h"
+#include <deque>
 #include <string>
 #include "../../include/OptAmd.h"
 
@@ -243,7 +244,17 @@ struct EnergyInfo {
     int residualsPerEdge = 0;
     EnergyOps<float>* (*makeFloat)(const unsigned* dims);
     EnergyOps<double>* (*makeDouble)(const unsigned* dims);
+    // Body hashes (OptAmd_ProblemFileHash) of the .t versions this kernel set implements, beyond those of energy_hashes.inc: empty for the built-in energies (their
+    // table is generated), at least one for an energy a plug-in brings (include/OptAmdPlugin.h) -- a plug-in entry without a hash is refused when it is loaded.
+    std::vector<unsigned long> bodyHashes;
 };
-const std::vector<EnergyInfo>& energyRegistry();
+// Built-in energies first, in a fixed order; energies of loaded plug-ins behind them in loading order (OptAmd_LoadEnergyPlugin).  Entries are never removed or moved:
+// a pointer to one stays valid for the life of the process (std::deque).
+const std::deque<EnergyInfo>& energyRegistry();
+
+// The ABI between libOpt.so and an energy plug-in is the C++ layout of the types a kernel set is called through.  BUMP THIS whenever EnergyOps (its members or the order
+// or signature of its virtual functions), EnergyInfo, ParamDecl, LaunchCtx, Reduction, KernelTimer or OnchipGuard change; include/OptAmdPlugin.h combines it with the sizes
+// of those types as each side compiled them, and libOpt.so refuses a plug-in whose stamp differs from its own before it runs anything else of the plug-in.
+constexpr unsigned kEnergyAbiVersion = 1;
 
 }  // namespace optamd

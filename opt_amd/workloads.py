@@ -5,6 +5,7 @@ index each array / scalar has in the energy's .t file (what a caller puts in Opt
 The shapes mirror the reference example harnesses (cited per generator); there is no network, so image /
 mesh payloads are procedural.
 """
+import os
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -440,3 +441,23 @@ def robust_from_mesh(V, F, double=False, seed=0, perturb=0.0):
     return Problem("robust_nonrigid_alignment", (len(V),),
                    [np.float32(np.sqrt(10.0)), np.float32(np.sqrt(64.0)), off.astype(ft), ang.astype(ft), rw.astype(ft), V.astype(ft), cons.astype(ft), nrm.astype(ft),
                     np.array(len(heads), dtype=np.int32), heads, tails], (2, 3, 4), double, {"n_edges": int(len(heads))})
+
+
+SPRING_T = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "examples", "plugins", "spring_mesh_deformation.t"))
+
+
+def spring_from_mesh(V, F, pinned, lifted, double=False, seed=0, perturb=0.0, lift=(0.0, 0.3, 0.8)):
+    """examples/plugins/spring_mesh_deformation.t (an energy a plug-in brings, not one of the built-in twelve; its .t is SPRING_T): X = UrShape = vertex
+    positions (X perturbed by `perturb`), Constraints = -inf except handle vertices (`pinned` stay, `lifted` move by `lift`), one half-edge per
+    (vertex, ring neighbour); weights 3 / 12 like the embedded example's fit and regularisation."""
+    from . import io
+    ft = np.float64 if double else np.float32
+    V = np.asarray(V, dtype=np.float64)
+    rng = np.random.default_rng(seed + 5)
+    heads, tails = _half_edges_from_rings(io.mesh_vertex_rings(len(V), F))
+    X = V + (rng.normal(0, perturb, size=V.shape) if perturb > 0 else 0)
+    cons = np.full(V.shape, -np.inf)
+    cons[pinned] = V[pinned]; cons[lifted] = V[lifted] + np.array(lift)
+    return Problem("spring_mesh_deformation", (len(V),),
+                   [X.astype(ft), V.astype(ft), cons.astype(ft), np.float32(np.sqrt(3.0)), np.float32(np.sqrt(12.0)),
+                    np.array(len(heads), dtype=np.int32), heads, tails], (0,), double, {"n_edges": int(len(heads))})

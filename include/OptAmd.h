@@ -162,6 +162,17 @@ int OptAmd_PlanDescribe(Opt_Plan* plan, char* out, int outLen);
  *                          cotangent is SLOWER everywhere (raptor GN 27.4 -> 44.1, LM 33.0 -> 48.9, 512 x 512 115.3 -> 185.4): four slots per hyperedge mean four
  *                          evaluations of its normalisations and square roots per hyperedge where the edge pass does one.  Set it for embedded_mesh_deformation and
  *                          robust_nonrigid_alignment, not for cotangent_mesh_smoothing.
+ *   "amd_stencil_fused"    0 (default): nothing changes.  1: the energies on the functor stencil engine (stencil_engine.h) run TWO launches per PCG iteration where their
+ *                          launch-per-iteration loop otherwise runs the reference's three (PCGStep1, PCGStep2, PCGStep3): ge_flatStep (PCGStep2 + PCGStep3 of the
+ *                          previous iteration, beta's numerator by expansion; ge_flatStepNoPre for an energy that does not precondition) and se_gatherIter (PCGStep1:
+ *                          se_gather's J^T J p, the same bits, plus the sums the next flat pass needs).  That loop serves image-domain plug-ins (OptAmdPlugin.h
+ *                          stencilEnergyInfo), volumetric_mesh_deformation under OPT_AMD_VOLUMETRIC_ARAP=0, and optical_flow / intrinsic_image_decomposition wherever
+ *                          neither an on-chip solve nor the marching Gauss-Newton loop takes the linear solve (Levenberg-Marquardt off chip, e.g. "amd_onchip" = 0 or
+ *                          an image past the on-chip range).  Gauss-Newton and Levenberg-Marquardt (paired deltaOut, tagged Q, the restart behind a split residual
+ *                          reset), float and double, one GPU (row slabs keep the three launches).  The loop sums in another order and takes beta's numerator by
+ *                          expansion, so a solve rounds differently: opt-in.  "amd_reference_order" = 1 wins; other energies ignore it.  OptAmd_PlanDescribe says
+ *                          `launches_per_iteration=2; kernels=ge_flatStep+se_gatherIter<T, functor, GN|LM>`, or `why_not_fused=` with the reason.  Measured:
+ *                          profiles/stencil_fused.md (DESIGN.md section 3.6 quotes it, losses included).
  * OptAmd_PlanDescribe reports the choice.  (The environment switches OPT_AMD_ONEKERNEL / OPT_AMD_ONCHIP remain as process-wide development overrides.) */
 
 /* The float4 copy rate of this box in GB/s: `bytes` moved in total per repetition (half read, half written; device memory allocated and freed inside the call),

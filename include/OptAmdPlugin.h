@@ -5,7 +5,7 @@
  * After OptAmd_LoadEnergyPlugin (OptAmd.h; or OPT_AMD_ENERGY_PLUGINS) the energy's .t file is planned, probed and solved through the unmodified Opt_* API.
  * This header is C++ (HIP): it is what a plug-in SOURCE includes, never what a caller of the library includes.
  *
- * A plug-in source for a mesh energy is (examples/plugins/spring_mesh_deformation.hip is the worked example; compile it with opt_amd/build.py build_plugin):
+ * A plug-in source for a MESH energy is (examples/plugins/spring_mesh_deformation.hip is the worked example; compile it with opt_amd/build.py build_plugin):
  *
  *     #pragma clang fp contract(off)          // (the engine's kernels expect the functor's arithmetic as written)
  *     #include "OptAmdPlugin.h"
@@ -39,6 +39,43 @@
  * S is T or a dual number over T (stencil_engine.h Dual: + - * /, sqrt, sin, cos, valueOf): write the residuals once, with the .t's expressions; the engine
  * differentiates them.  A condition on a value takes valueOf(s).  Inputs that are not unknowns are read as plain T from the functor's own pointers.
  * The tuning constants of the on-chip solves come from GraphFunctorDefaults below unless the functor declares its own.
+ *
+ * A plug-in source for an IMAGE-DOMAIN energy (a 2-D or 3-D index space; examples/plugins/vector_tv_denoising.hip is the worked example) differs in its includes, its
+ * functor and its registration call:
+ *
+ *     #include "OptAmdPlugin.h"
+ *     #include "stencil_engine.h"             // cost, J^T F, J^T J p, model cost; three or two launches per PCG iteration (amd_stencil_fused)
+ *     #include "graph_pcg.h"                  // ... whose flat pass (ge_flatStep) and host side live here (stencil_engine.h includes it; named for the reader)
+ *     ... EnergyInfo e = stencilEnergyInfo<MyE, true>("my_energy"); ...
+ *
+ * What a stencil functor E provides (stencil_engine.h instantiates every kernel from it; T is float or double):
+ *   static constexpr int   NDIM            dimensions of the index space (2 or 3; entries of `dimensions` consumed: W, H [, D])
+ *   static constexpr int   NIMG            number of unknown images
+ *   static constexpr int   K               unknown scalars per pixel, all images together
+ *   static constexpr int   R               scalar residuals per pixel (every Energy(...) row, vector rows counted per channel, stencil rows per offset)
+ *   static constexpr int   NOFF            stencil offsets at which a residual reads an UNKNOWN, the centre included
+ *   static constexpr int   NAUX            planes of ComputedArrays (0: none); with NAUX > 0 the engine owns `aux` (plane k at aux + k W H D) and fills it
+ *                                          with computeAux after bind and after every update or revert
+ *   static constexpr       off(i, axis)    offset i along axis 0 / 1 / 2 (x / y / z); off(0, .) == 0: offset 0 is the centre  (__host__ __device__)
+ *   static constexpr       imgOf(k), chOf(k), channels(img)      which image and channel unknown k of a pixel is; channels of an image  (__host__ __device__)
+ *   static constexpr bool  depends(ri, oi) may residual ri depend on the unknowns at offset oi?  (true is always correct; false prunes derivative work)
+ *   static constexpr const char* kName     the name OptAmd_PlanDescribe prints in the kernel variant
+ *   static int             unknownParam(img)        binding index of unknown image img
+ *   members                int W, H, D; const T* X[NIMG]; T* aux;      the index space (set by the engine; 1 beyond NDIM), the unknown images, the aux planes
+ *   void bindParams(void** problemparams)  host: read every pointer and host scalar (Params are float on the host whatever T is)
+ *   __device__ bool excluded(int x, int y, int z) const          restates the .t's Exclude(...): the pixel is not an unknown (its rows of J^T F, diag and
+ *                                          J^T J p are 0, the residuals centred on it do not count in the cost but do count for its neighbours)
+ *   __device__ void computeAux(int x, int y, int z, T* out) const      out[0..NAUX): the ComputedArrays at the pixel, from the current unknowns
+ *   template <class S, class C> __device__ void residuals(const C& Xc, int x, int y, int z, S* r) const      r[0..R) of the residuals CENTRED at (x, y, z):
+ *                                          Xc(k, dx, dy, dz) is unknown k at that offset from the centre as an S (0 outside the image, like the reference's
+ *                                          image loads), Xc.in(dx, dy, dz) says whether the offset is inside the image
+ * A residual whose stencil leaves the image is the functor's business: it must restate the InBounds / default-zero rule of its .t (typically
+ * r[i] = Xc.in(dx, dy, 0) ? e : S(T(0))).  Every offset passed to Xc must be one of off(i, .).  S is T or a dual number over T, as for graph functors; the helpers
+ * are valueOf(s) (the plain value, for conditions and for sampling positions), chain1(f, f', u) and chain2(f, fu, fv, u, v) (a function of one or two unknowns
+ * whose value and partials are known: a table, a sampled image).  StencilFunctorDefaults<T> below supplies NAUX = 0, aux, an empty computeAux and
+ * excluded() == false for a functor that needs none of them.
+ * Image-domain plug-ins run the engine's launch-per-iteration loops only.  The marching Gauss-Newton loop (stencil_march.h) and the on-chip stencil solves
+ * (stencil_onchip.h) need a hand-written 5-point operator besides the functor and are not offered to plug-in sources.
  *
  * The .t and the hash rule.  The .t file is what the caller passes to Opt_ProblemDefine, written as the reference would accept it; libOpt.so reads its
  * declarations (they must match `params`: kind, name, type, binding index; and UsePreconditioner) and hashes its body.  Only a body whose hash the entry
@@ -103,6 +140,29 @@ EnergyInfo graphEnergyInfo(const char* name) {
     e.name = name; e.nDims = 1; e.usePreconditioner = USE_PRECONDITIONER; e.floatOnly = false;
     e.residualsPerElement = G<float>::RV; e.residualsPerEdge = G<float>::RE;
     e.makeFloat = makeGraphOps<G, USE_PRECONDITIONER, float>; e.makeDouble = makeGraphOps<G, USE_PRECONDITIONER, double>;
+    return e;
+}
+
+/* What a stencil functor that has no ComputedArrays and excludes nothing need not write itself (redeclare a member in the functor to override it). */
+template <class T>
+struct StencilFunctorDefaults {
+    static constexpr int NAUX = 0;
+    T* aux;
+    __device__ void computeAux(int, int, int, T*) const {}
+    __device__ bool excluded(int, int, int) const { return false; }
+};
+
+/* The registry entry of an image-domain energy over one 2-D or 3-D index space, served by the stencil engine instantiated for the functor template E.  `params` and
+ * `bodyHashes` are the author's to fill in.  (The source includes stencil_engine.h before it calls this.) */
+template <class T, class E> struct StencilOps;
+template <template <class> class E, bool USE_PRECONDITIONER, class T>
+EnergyOps<T>* makeStencilOps(const unsigned* dims) { return new StencilOps<T, E<T>>(dims, USE_PRECONDITIONER); }
+template <template <class> class E, bool USE_PRECONDITIONER>
+EnergyInfo stencilEnergyInfo(const char* name) {
+    EnergyInfo e;
+    e.name = name; e.nDims = E<float>::NDIM; e.usePreconditioner = USE_PRECONDITIONER; e.floatOnly = false;
+    e.residualsPerElement = E<float>::R;
+    e.makeFloat = makeStencilOps<E, USE_PRECONDITIONER, float>; e.makeDouble = makeStencilOps<E, USE_PRECONDITIONER, double>;
     return e;
 }
 

@@ -119,7 +119,7 @@ def check_problem_file(path):
     return bool(ok), buf.value.decode()
 
 
-_INT_PARAMS = {"nIterations", "lIterations", "residual_reset_period", "nIter", "patchIterations", "patchSize", "amd_reference_order", "amd_onchip", "amd_onchip_workgroups", "amd_graph_fused"}
+_INT_PARAMS = {"nIterations", "lIterations", "residual_reset_period", "nIter", "patchIterations", "patchSize", "amd_reference_order", "amd_onchip", "amd_onchip_workgroups", "amd_graph_fused", "amd_stencil_fused"}
 
 
 def energy_file(stem):

@@ -99,13 +99,15 @@ def build(force=False, verbose=False):
     build_comm(force=force, verbose=verbose)
     build_examples(force=force, verbose=verbose)
     build_plugin(SAMPLE_PLUGIN, force=force, verbose=verbose)
+    build_plugin(SAMPLE_STENCIL_PLUGIN, force=force, verbose=verbose)
     return LIB
 
 
 # ---- energy plug-ins (include/OptAmdPlugin.h): one .hip source -> one shared object that libOpt.so loads at run time --------------------------------------------
 PLUGIN_LIBDIR = os.path.join(LIBDIR, "plugins")
 PLUGIN_OBJDIR = os.path.join(HERE, "build_plugins")      # NOT build/: kernel_resources() reads every *.remarks there as libOpt.so's
-SAMPLE_PLUGIN = os.path.join(HERE, "..", "examples", "plugins", "spring_mesh_deformation.hip")
+SAMPLE_PLUGIN = os.path.join(HERE, "..", "examples", "plugins", "spring_mesh_deformation.hip")            # a mesh energy (graph functor)
+SAMPLE_STENCIL_PLUGIN = os.path.join(HERE, "..", "examples", "plugins", "vector_tv_denoising.hip")      # an image-domain energy (stencil functor)
 
 
 def plugin_path(stem):

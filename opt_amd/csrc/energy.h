@@ -193,6 +193,9 @@ struct EnergyOps {
     // The plan's amd_graph_fused, already combined with amd_reference_order == 0 (which wins over every path selection), handed over with onChipLevel: the functor
     // mesh energies (graph_engine.h) then run two launches per PCG iteration and J^T J p without records; every other kernel set ignores it
     bool graphFused = false;
+    // The plan's amd_stencil_fused, combined with amd_reference_order == 0 in the same way: the functor stencil energies (stencil_engine.h) then run two launches per
+    // PCG iteration (ge_flatStep + se_gatherIter) where the default runs the reference's three; every other kernel set ignores it
+    bool stencilFused = false;
     // Row slabs, behind a pcgSolveOnChip launch (which then applies nothing itself): onChipVerdict leaves this rank's verdict (0 fine / 1 failed) in a device scalar, the
     // solver all-reduces it, onChipApply applies X += delta iff the sum is 0 -- every rank keeps its update or none does -- and tells the host (OnchipGuard::failedNow).
     virtual void onChipVerdict(double* /*out*/, bool /*refused*/, LaunchCtx&) {}
@@ -225,6 +228,9 @@ struct EnergyOps {
     // slab tiling (image energies): number of scalars in one image row of unknown image `img`
     virtual bool supportsSlab() const { return false; }
     virtual long rowScalars(int /*img*/) const { return 0; }
+    // What describe() adds about the kernel set's own launch-per-iteration loop where another path (an on-chip solve, a marching loop) is described first:
+    // "; key=value ..." or nothing.  The functor stencil engine says here whether that loop runs two launches per PCG iteration (amd_stencil_fused) or why not.
+    virtual std::string perIterationNote(bool /*lm*/) const { return std::string(); }
 };
 
 // Registry entry: what a .t file must declare for this kernel set, and how to instantiate it.
@@ -255,6 +261,6 @@ const std::deque<EnergyInfo>& energyRegistry();
 // The ABI between libOpt.so and an energy plug-in is the C++ layout of the types a kernel set is called through.  BUMP THIS whenever EnergyOps (its members or the order
 // or signature of its virtual functions), EnergyInfo, ParamDecl, LaunchCtx, Reduction, KernelTimer or OnchipGuard change; include/OptAmdPlugin.h combines it with the sizes
 // of those types as each side compiled them, and libOpt.so refuses a plug-in whose stamp differs from its own before it runs anything else of the plug-in.
-constexpr unsigned kEnergyAbiVersion = 1;
+constexpr unsigned kEnergyAbiVersion = 2;      // 2: EnergyOps::stencilFused, EnergyOps::perIterationNote
 
 }  // namespace optamd

@@ -15,6 +15,7 @@ namespace {
 // e_reg = w_reg (X(0,0) - X(n)) for the 4-neighbourhood, Select(InBounds(n), ., 0).  UsePreconditioner(false).
 template <class T>
 struct OpticalFlowE {
+    static constexpr const char* kName = "OpticalFlowE";
     static constexpr int NDIM = 2, NIMG = 1, K = 2, R = 9, NOFF = 5, NAUX = 0;
     static constexpr __host__ __device__ int off(int i, int a) { return a == 0 ? (i == 1 ? 1 : i == 2 ? -1 : 0) : a == 1 ? (i == 3 ? 1 : i == 4 ? -1 : 0) : 0; }
     static constexpr __host__ __device__ int imgOf(int) { return 0; }
@@ -64,6 +65,7 @@ struct OpticalFlowE {
 // No UsePreconditioner call -> false; no Exclude.
 template <class T>
 struct IntrinsicE {
+    static constexpr const char* kName = "IntrinsicE";
     static constexpr int NDIM = 2, NIMG = 2, K = 4, R = 19, NOFF = 5, NAUX = 4;      // four L_p weight planes, one per stencil direction
     static constexpr __host__ __device__ int off(int i, int a) { return a == 0 ? (i == 1 ? 1 : i == 2 ? -1 : 0) : a == 1 ? (i == 3 ? 1 : i == 4 ? -1 : 0) : 0; }
     static constexpr __host__ __device__ int imgOf(int k) { return k < 3 ? 0 : 1; }
@@ -120,6 +122,7 @@ struct IntrinsicE {
 // (lib.t:77-91), Select(InBounds(0,0,0), Select(InBounds(n), ., 0), 0).  UsePreconditioner(true).
 template <class T>
 struct VolumetricE {
+    static constexpr const char* kName = "VolumetricE";
     static constexpr int NDIM = 3, NIMG = 2, K = 6, R = 21, NOFF = 7, NAUX = 6;      // sin and cos of the three angles: every residual centre a voxel's gather
                                                                                      // visits needs them (21 sincos per voxel per J^T J p otherwise)
     static constexpr __host__ __device__ int off(int i, int a) {

@@ -300,35 +300,7 @@ __global__ __launch_bounds__(kBlock) void ge_gather(G g, const T* __restrict__ v
     if (threadIdx.x == 0 && partials) partials[blockIdx.x] = t;
 }
 
-// PCGStep2 + PCGStep3 of the previous iteration in one flat pass over the padded scalars: the scalars of graph_flat_scalars.inc, LM's extras of graph_pcg.h (LmStep), the
-// update in a grid-stride loop.  Energy-independent: arap_flatStepPlanes without the planes.
-template <class T, bool LM>
-__global__ __launch_bounds__(kBlock) void ge_flatStep(long n, T* __restrict__ delta, const T* __restrict__ pOld, const T* __restrict__ rOld, const T* __restrict__ Ap, const T* __restrict__ M,
-                                                       T* __restrict__ rNew, T* __restrict__ pNew, const double* aNumP, int nNum, const double* aDenP, int nDen,
-                                                       const double* s2P, int n2, const double* s3P, int n3, LmStep<T> L) {
-    __shared__ double scratch[4 * (kBlock / kWave + 1)];
-#include "graph_flat_scalars.inc"      // alpha, beta, restart
-    T* const dOut = LM ? L.deltaOut : delta;
-    double accQ = 0;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const T p = pOld[i], r = rOld[i], m = M[i];
-        T rn, pn;
-        if (restart) { rn = r; pn = m * r + beta * p; }
-        else {
-            const T d = delta[i] + alpha * p;
-            rn = r - alpha * Ap[i];
-            const T z = m * rn;
-            pn = z + beta * p;
-            if (LM) accQ += (double)(T(0.5) * (d * (rn + L.b[i])));
-            dOut[i] = d;
-        }
-        rNew[i] = rn; pNew[i] = pn;
-    }
-    if (LM && L.q && !restart) {
-        const double tq = blockReduceSum(accQ, scratch);
-        if (threadIdx.x == 0) { if (L.qTag) storeTaggedPartial(L.q, blockIdx.x, tq, L.qTag); else L.q[blockIdx.x] = tq; }
-    }
-}
+// (PCGStep2 + PCGStep3 of the previous iteration in one flat pass: ge_flatStep, energy-independent, is graph_pcg.h's -- the stencil engine runs it too)
 
 // ---- the whole linear solve in one workgroup (solver parameter amd_onchip = 6): the kernel and its variant list are graph_onchip.h, which the file that defines the
 // functors includes behind this one ----

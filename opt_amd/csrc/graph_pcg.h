@@ -1,9 +1,12 @@
 // What the PCG kernels of the graph kernel sets share, each piece written once: the value types and derivative columns of ARAP's gather (arap_applyEll, arap_onchipPcg;
 // the body of the walk is arap_half_edge_pair.inc), the argument structs, the term and the store of the sums of a two-launch iteration (arap_applyEll, ge_gather,
 // arap_onchipPcg), LM's extras of the flat PCGStep2 + PCGStep3 pass (arap_flatStepPlanes, ge_flatStep; its scalars are graph_flat_scalars.inc) and the host side of
-// such an iteration (ArapOps::pcgIteration, GraphOps::pcgIteration).  Every device piece is a force-inlined function on plain values; a kernel keeps its own loop, layout,
+// such an iteration (ArapOps::pcgIteration, GraphOps::pcgIteration, StencilOps::pcgIteration) -- and, at the end of the file, the two energy-independent kernels of
+// that pass themselves, ge_flatStep and ge_flatStepNoPre, which both functor engines launch (graph_engine.h, stencil_engine.h).  Every device piece is a force-inlined
+// function on plain values; a kernel keeps its own loop, layout,
 // grid and walk order, and the order in which it adds the terms it gets from here.  No pragma in this file: it is compiled with the contraction setting of the file
-// that includes it (energy_graph_functors.hip: off).  Every kernel but arap_applyFused, which lost dead code, compiles to the instructions it had before these pieces
+// that includes it (energy_graph_functors.hip and plug-in sources: off; energy_functors.hip: the compiler's default).  The kernels take LmStep, a type of this file's
+// unnamed namespace, so every translation unit launches its own copy.  Every kernel but arap_applyFused, which lost dead code, compiles to the instructions it had before these pieces
 // were shared; what else was tried as a function, and what the compiler made of it: profiles/graph_shared_text.md.
 #pragma once
 #include "graph_common.h"
@@ -83,4 +86,84 @@ void pcgTwoLaunchIteration(const PcgIterArgs<T>& a, long nPad, LaunchCtx& ctx, F
 }
 
 }  // namespace
+
+// PCGStep2 + PCGStep3 of the previous iteration in one flat pass over the padded scalars: the scalars of graph_flat_scalars.inc, LM's extras (LmStep), the
+// update in a grid-stride loop.  Energy-independent: arap_flatStepPlanes without the planes.  Launched by both functor engines (graph_engine.h GraphOps::pcgIteration,
+// stencil_engine.h StencilOps::pcgIteration).
+template <class T, bool LM>
+__global__ __launch_bounds__(kBlock) void ge_flatStep(long n, T* __restrict__ delta, const T* __restrict__ pOld, const T* __restrict__ rOld, const T* __restrict__ Ap, const T* __restrict__ M,
+                                                       T* __restrict__ rNew, T* __restrict__ pNew, const double* aNumP, int nNum, const double* aDenP, int nDen,
+                                                       const double* s2P, int n2, const double* s3P, int n3, LmStep<T> L) {
+    __shared__ double scratch[4 * (kBlock / kWave + 1)];
+#include "graph_flat_scalars.inc"      // alpha, beta, restart
+    T* const dOut = LM ? L.deltaOut : delta;
+    double accQ = 0;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const T p = pOld[i], r = rOld[i], m = M[i];
+        T rn, pn;
+        if (restart) { rn = r; pn = m * r + beta * p; }
+        else {
+            const T d = delta[i] + alpha * p;
+            rn = r - alpha * Ap[i];
+            const T z = m * rn;
+            pn = z + beta * p;
+            if (LM) accQ += (double)(T(0.5) * (d * (rn + L.b[i])));
+            dOut[i] = d;
+        }
+        rNew[i] = rn; pNew[i] = pn;
+    }
+    if (LM && L.q && !restart) {
+        const double tq = blockReduceSum(accQ, scratch);
+        if (threadIdx.x == 0) { if (L.qTag) storeTaggedPartial(L.q, blockIdx.x, tq, L.qTag); else L.q[blockIdx.x] = tq; }
+    }
+}
+
+// The same pass for an energy that does not precondition (UsePreconditioner(false): the solver hands pcgIteration no M): M == 1 at compile time, no load of it.
+// The first pass of a linear solve differs from the later ones in one scalar.  The reference starts such a solve from p_0 = M_0 r_0 with a vector M_0 that is not 1
+// (PCGInit1: guardedInvert(1) = 1/4; Levenberg-Marquardt: PCGFinalizeDiagonal's preconditioner) and alphaNumerator_0 = r_0 . p_0, and continues with z = r.  The
+// gather of the first launch therefore leaves r_0 . p_0 as its alphaNumerator -- what alpha_0 = aNum / aDen and beta_0's denominator are -- and sum r_0^2, which the
+// expansion of beta_0's numerator sum (r_0 - alpha A p_0)^2 = sum r_0^2 - 2 alpha s2 + alpha^2 s3 starts from, apart in rr0P (nullptr on every later pass, where
+// the two are the same sum).  The arithmetic is graph_flat_scalars.inc's with that one term exchanged; the restart after a split residual reset is unchanged.
+template <class T, bool LM>
+__global__ __launch_bounds__(kBlock) void ge_flatStepNoPre(long n, T* __restrict__ delta, const T* __restrict__ pOld, const T* __restrict__ rOld, const T* __restrict__ Ap,
+                                                            T* __restrict__ rNew, T* __restrict__ pNew, const double* aNumP, int nNum, const double* aDenP, int nDen,
+                                                            const double* s2P, int n2, const double* s3P, int n3, const double* rr0P, int nrr0, LmStep<T> L) {
+    __shared__ double scratch[4 * (kBlock / kWave + 1)];
+    T alpha, beta;
+    const bool restart = LM && L.afterReset;
+    if (restart) {
+        const double* const ps[2] = {L.bNumP, L.bDenP}; const int ns[2] = {L.nbNum, L.nbDen}; double o2[2];
+        sumPartialsN<2>(ps, ns, scratch, o2);
+        const T bNum = (T)o2[0], bDen = (T)o2[1];
+        alpha = T(0); beta = (bDen > T(0)) ? bNum / bDen : T(0);                            // PCGStep3's guard (solver.t:544-547)
+    } else {
+        const double* const ps[4] = {aNumP, aDenP, s2P, s3P}; const int ns[4] = {nNum, nDen, n2, n3}; double o4[4];
+        sumPartialsN<4>(ps, ns, scratch, o4);
+        const double rr = rr0P ? sumPartials(rr0P, nrr0, scratch) : o4[0];                   // (a kernel argument: uniform)
+        const T aNum = (T)o4[0], aDen = (T)o4[1];
+        alpha = (aDen > T(0)) ? aNum / aDen : T(0);                                          // solver.t:456-459
+        const double bNumD = fmax(rr - 2.0 * (double)alpha * o4[2] + (double)alpha * (double)alpha * o4[3], 0.0);
+        beta = (aNum > T(0)) ? (T)bNumD / aNum : T(0);                                       // solver.t:544-547
+    }
+    T* const dOut = LM ? L.deltaOut : delta;
+    double accQ = 0;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const T p = pOld[i], r = rOld[i];
+        T rn, pn;
+        if (restart) { rn = r; pn = r + beta * p; }
+        else {
+            const T d = delta[i] + alpha * p;
+            rn = r - alpha * Ap[i];
+            pn = rn + beta * p;
+            if (LM) accQ += (double)(T(0.5) * (d * (rn + L.b[i])));
+            dOut[i] = d;
+        }
+        rNew[i] = rn; pNew[i] = pn;
+    }
+    if (LM && L.q && !restart) {
+        const double tq = blockReduceSum(accQ, scratch);
+        if (threadIdx.x == 0) { if (L.qTag) storeTaggedPartial(L.q, blockIdx.x, tq, L.qTag); else L.q[blockIdx.x] = tq; }
+    }
+}
+
 }  // namespace optamd

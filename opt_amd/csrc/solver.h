@@ -28,7 +28,8 @@ struct SolverParameters {
                                   // any horizon; ~3x the bytes of the default single-kernel iteration and never on chip.
     int amd_onchip = 1;           // 0: never take the on-chip (persistent) linear solve; 1: take it where the problem fits (default); 2: as 1, and the 5-point-stencil energies keep an LM solve on chip when a residual reset falls inside it; 3: as 2, and shape_from_shading too; 4: as 3, and image_warping takes the on-chip solve for any UrShape (not only the unit lattice); 5: as 4, and arap_mesh_deformation (volumetric_mesh_deformation too) runs the whole linear solve of a small symmetric graph in one workgroup; 6: as 5, and the functor mesh energies (cotangent, embedded, robust) run the whole linear solve of a small mesh in one workgroup too (graph_onchip.h); 7: as 6, and those energies may run it as one persistent launch of several workgroups (graph_onchip_grid.h; amd_onchip_workgroups)
     int amd_onchip_workgroups = 0;      // consulted at amd_onchip = 7 only (the functor mesh energies' linear solve as one persistent launch of several workgroups, graph_onchip_grid.h): 0 (default): the plan decides (GraphOps::ggAutoWorkgroups); n >= 1: n workgroups, clamped to one vertex per workgroup and to the family's cap of 32
-    int amd_graph_fused = 0;      // 1: cotangent_mesh_smoothing, embedded_mesh_deformation and robust_nonrigid_alignment run two launches per PCG iteration (ge_flatStep + ge_gather, graph_engine.h) and J^T J p without the per-(hyperedge, slot) records; 0 (default): the reference-order loop on the record kernels.  Opt-in: the fused loop sums in another order and takes beta's numerator by expansion.  amd_reference_order = 1 wins; other energies ignore it
+    int amd_stencil_fused = 0;    // 1: the energies on the functor stencil engine (stencil_engine.h: optical_flow and intrinsic_image_decomposition wherever they run its launch-per-iteration loop, volumetric_mesh_deformation with OPT_AMD_VOLUMETRIC_ARAP=0, image-domain plug-ins) run two launches per PCG iteration (ge_flatStep + se_gatherIter); 0 (default): the reference's three.  Opt-in: the loop sums in another order and takes beta's numerator by expansion.  amd_reference_order = 1 wins; on-chip solves and the marching loops keep precedence; other energies ignore it
+    int amd_graph_fused = 0;     // 1: cotangent_mesh_smoothing, embedded_mesh_deformation and robust_nonrigid_alignment run two launches per PCG iteration (ge_flatStep + ge_gather, graph_engine.h) and J^T J p without the per-(hyperedge, slot) records; 0 (default): the reference-order loop on the record kernels.  Opt-in: the fused loop sums in another order and takes beta's numerator by expansion.  amd_reference_order = 1 wins; other energies ignore it
 };
 
 struct SolverBase {

@@ -730,7 +730,8 @@ struct PcgSolver : SolverBase {
         lastStepOnChip = false;
         sp.nIter = f;
     }
-    void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipWorkgroups = sp.amd_onchip_workgroups; E->onChipPre = preconditioner; E->graphFused = sp.amd_graph_fused != 0 && sp.amd_reference_order == 0; }      // (EnergyOps::onChipLevel, graphFused)
+    void tellOnChipLevel() { E->onChipLevel = sp.amd_onchip; E->onChipWorkgroups = sp.amd_onchip_workgroups; E->onChipPre = preconditioner; E->graphFused = sp.amd_graph_fused != 0 && sp.amd_reference_order == 0;
+                             E->stencilFused = sp.amd_stencil_fused != 0 && sp.amd_reference_order == 0; }      // (EnergyOps::onChipLevel, graphFused, stencilFused)
     int stepOnce(void** params, bool& again) {
         tellOnChipLevel();
         if (!boundOncePerSolve()) E->bind(params, ctx);
@@ -978,6 +979,7 @@ struct PcgSolver : SolverBase {
         tellOnChipLevel();
         std::string d = sp.amd_reference_order ? std::string("path=reference-order (PCGStep1 [+ the previous PCGStep3] and PCGStep2 per PCG iteration, r / z / A p in memory); amd_reference_order=1")
                                                : [&] { const OnChipLm<T> la = lmControls(); return E->describe(sp.lIterations, lm, lm ? &la : nullptr); }();
+        if (sp.amd_reference_order && sp.amd_stencil_fused) d += "; why_not_fused=amd_reference_order wins over amd_stencil_fused";
         if (!sp.amd_reference_order && sp.amd_onchip != 1) d += "; amd_onchip=" + std::to_string(sp.amd_onchip);
         if (!sp.amd_reference_order && !oneKernel) d += "; OPT_AMD_ONEKERNEL=0 (reference-order loop by environment)";
         if (onChipFailures) d += "; onchip_fallbacks=" + std::to_string(onChipFailures) + "; onchip_backoff_steps_left=" + std::to_string(onChipOff() ? onChipBackoff - onChipCleanSteps : 0);
@@ -1054,7 +1056,7 @@ bool SolverBase::setParameter(const char* name, const void* value) {   // solver
     PF(min_relative_decrease) PF(min_trust_region_radius) PF(max_trust_region_radius) PF(q_tolerance) PF(function_tolerance)
     PF(trust_region_radius) PF(radius_decrease_factor) PF(min_lm_diagonal) PF(max_lm_diagonal)
     PI(residual_reset_period) PI(nIter) PI(nIterations) PI(lIterations) PI(patchIterations) PI(patchSize)
-    PI(amd_reference_order) PI(amd_onchip) PI(amd_onchip_workgroups) PI(amd_graph_fused)
+    PI(amd_reference_order) PI(amd_onchip) PI(amd_onchip_workgroups) PI(amd_graph_fused) PI(amd_stencil_fused)
 #undef PF
 #undef PI
     return false;

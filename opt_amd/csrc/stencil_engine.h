@@ -17,8 +17,11 @@
 // excluded pixel count in J^T F / J^T J of their non-excluded neighbours but not in the cost (solver.t:583 vs o.t:2029-2089);
 // rows of excluded unknowns are 0.  Whether a residual whose stencil leaves the image is dropped is the functor's business
 // (it must restate the InBounds / default-zero rule of its .t).
+// Solver parameter amd_stencil_fused = 1: the PCG iteration as two launches (graph_pcg.h ge_flatStep / ge_flatStepNoPre + se_gatherIter below) through the solver's
+// launch-per-iteration loops, where the default runs the reference's three (se_gather, PCGStep2, PCGStep3).
 #pragma once
 #include "energy.h"
+#include "graph_pcg.h"      // the flat pass, the sums and the host side of a two-launch iteration: energy-independent, shared with graph_engine.h
 
 namespace optamd {
 
@@ -70,7 +73,7 @@ template <class T> __device__ __forceinline__ T part0(T) { return T(0); }      /
 
 // ---- accessors handed to the functor ----------------------------------------------------------------------------------
 // E (the energy functor type) provides, all constexpr / static:
-//   K, R, NOFF, NIMG;  off(i, axis) the stencil offsets (i = 0 is the centre);  imgOf(k), chOf(k), channels(img);
+//   K, R, NOFF, NIMG;  off(i, axis) the stencil offsets (i = 0 is the centre);  imgOf(k), chOf(k), channels(img);  kName (for OptAmd_PlanDescribe);
 //   depends(ri, oi): may residual ri depend on the unknowns at offset oi (lets the compiler drop the others);
 // and members W, H, D, X[NIMG] (caller arrays of the unknown images), plus whatever inputs it needs.
 template <class T, class E>
@@ -223,6 +226,50 @@ __global__ __launch_bounds__(kBlock) void se_gather(E e, const T* __restrict__ v
     }
 }
 
+// The Step1 half of a two-launch PCG iteration (solver parameter amd_stencil_fused = 1; graph_pcg.h): se_gather<T, E, true> -- the same walk, the same CtC term, the same
+// zero on excluded rows, hence the same bits in `out` -- whose thread also adds, for every scalar it owns, the terms of the sums the next flat pass needs (IterSums:
+// M r^2, M r . A p, M (A p)^2, products in double) from the r and M = pre it is handed; the workgroup leaves the four partials through storeIterSums.  PRE = false: the
+// energy does not precondition, M == 1 (S.M is not read).  Then the FIRST launch of a linear solve (rr0 != nullptr) leaves r . p_0 as its alphaNumerator and sum r^2
+// apart in rr0 (one partial per workgroup): see ge_flatStepNoPre.  A kernel of its own: se_gather's instantiations keep their registers.
+template <class T, class E, bool LM, bool PRE>
+__global__ __launch_bounds__(kBlock) void se_gatherIter(E e, const T* __restrict__ v, VOff<E> vo, T* __restrict__ out, const T* __restrict__ CtC, double* __restrict__ partials,
+                                                        IterSums<T> S, double* __restrict__ rr0) {
+    __shared__ double scratch[4 * (kBlock / kWave + 1)];
+    const long N = (long)e.W * e.H * e.D;
+    double acc = 0, accNum = 0, acc2 = 0, acc3 = 0, accRR = 0;
+    for (long c = blockIdx.x * (long)blockDim.x + threadIdx.x; c < N; c += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(c % e.W), y = (int)((c / e.W) % e.H), z = (int)(c / ((long)e.W * e.H));
+        T g[E::K], d[E::K];
+#pragma unroll
+        for (int k = 0; k < E::K; ++k) { g[k] = 0; d[k] = 0; }
+        const bool ex = e.excluded(x, y, z);
+        if (!ex) GatherStep<T, E, 0, true>::run(e, x, y, z, v, vo.o, g, d);
+#pragma unroll
+        for (int k = 0; k < E::K; ++k) {
+            const long i = vo.o[E::imgOf(k)] + c * E::channels(E::imgOf(k)) + E::chOf(k);
+            T s = g[k];
+            if (LM) s += CtC[i] * v[i];
+            if (ex) s = 0;
+            out[i] = s;
+            acc += (double)(v[i] * s);
+            const T rr = S.r[i];
+            if constexpr (PRE) {
+                const T m = S.M[i];
+                accNum += iterTerm(m, rr, rr); acc2 += iterTerm(m, rr, s); acc3 += iterTerm(m, s, s);
+            } else {
+                if (rr0) { accNum += iterTerm(T(1), rr, v[i]); accRR += iterTerm(T(1), rr, rr); }
+                else accNum += iterTerm(T(1), rr, rr);
+                acc2 += iterTerm(T(1), rr, s); acc3 += iterTerm(T(1), s, s);
+            }
+        }
+    }
+    if constexpr (!PRE) {
+        if (rr0) { const double t = blockReduceSum(accRR, scratch); if (threadIdx.x == 0) rr0[blockIdx.x] = t; }
+    }
+    double vv[4] = {acc, accNum, acc2, acc3};
+    storeIterSums(vv, partials, S, scratch);
+}
+
 // ---- EnergyOps on top of a functor ---------------------------------------------------------------------------------------
 // E must also provide (host):  void bindParams(void** params)  and  static int unknownParam(int img).
 template <class T, class E>
@@ -238,7 +285,7 @@ struct StencilOps : EnergyOps<T> {
         int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         if constexpr (E::NAUX > 0) { HIP_CHECK(hipMalloc((void**)&e.aux, (size_t)E::NAUX * n * sizeof(T))); HIP_CHECK(hipMemset(e.aux, 0, (size_t)E::NAUX * n * sizeof(T))); }
     }
-    ~StencilOps() override { if constexpr (E::NAUX > 0) (void)hipFree(e.aux); }
+    ~StencilOps() override { if constexpr (E::NAUX > 0) (void)hipFree(e.aux); if (iterRR0) (void)hipFree(iterRR0); }
     void precompute(LaunchCtx& ctx) override {
         if constexpr (E::NAUX > 0) { ScopedKernel k(ctx, "precompute"); se_precompute<T, E><<<grid(), kBlock, 0, ctx.stream>>>(e); }
     }
@@ -258,6 +305,58 @@ struct StencilOps : EnergyOps<T> {
     void evalModelCost(const T* delta, Reduction& out, LaunchCtx& ctx) override {
         ScopedKernel k(ctx, "computeModelCost"); se_modelCost<T, E><<<grid(), kBlock, 0, ctx.stream>>>(e, delta, vo, out.partials); out.n = grid();
     }
+    // ---- amd_stencil_fused = 1 (EnergyOps::stencilFused): the PCG iteration as ge_flatStep (ge_flatStepNoPre without a preconditioner) + se_gatherIter ----
+    // THE predicate of the path: nullptr, or why the plan keeps the three-launch loop.  pcgIteration and describe() both ask here.
+    const char* fusedWhyNot(bool lmWithoutBOrQ = false) const {
+        if (!this->stencilFused) return "amd_stencil_fused=1 was not set";
+        if (this->slab.active) return "row slabs";
+        if (lmWithoutBOrQ) return "Levenberg-Marquardt without b or q";
+        return nullptr;
+    }
+    double* iterRR0 = nullptr;       // PRE = false: sum r_0^2 of the first launch of a linear solve, one partial per workgroup (kMaxPartials doubles) ...
+    int iterRR0n = 0;                // ... how many, until the flat pass behind that launch has been given them (0: none pending)
+    template <bool LM, bool PRE>
+    int launchGatherIter(const PcgIterArgs<T>& a, const IterSums<T>& S, double* rr0, LaunchCtx& ctx) {
+        const int g = grid();
+        se_gatherIter<T, E, LM, PRE><<<g, kBlock, 0, ctx.stream>>>(e, a.pNew, vo, a.ApNew, a.CtC, a.aDen->partials, S, rr0);
+        return g;
+    }
+    bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
+        if (fusedWhyNot(a.CtC && !(a.b && a.q))) return false;
+        const long nPad = (this->nScalars + 3) / 4 * 4;      // the solver's vectors (zero beyond nScalars)
+        const int gf = flatGrid(nPad, cus, kMaxPartials / 2);
+        const bool pre = a.pre != nullptr;
+        if (!pre && !iterRR0) HIP_CHECK(hipMalloc((void**)&iterRR0, kMaxPartials * sizeof(double)));
+        pcgTwoLaunchIteration(a, nPad, ctx, [] {},
+            [&](bool lm, const LmStep<T>& L) {
+                if (pre)
+                    (lm ? ge_flatStep<T, true> : ge_flatStep<T, false>)<<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
+                        a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L);
+                else {      // (the pass behind the first launch of the solve: beta's expansion starts from sum r_0^2, which is not the alphaNumerator there)
+                    const int n0 = a.afterReset ? 0 : iterRR0n;
+                    (lm ? ge_flatStepNoPre<T, true> : ge_flatStepNoPre<T, false>)<<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
+                        a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, n0 ? iterRR0 : nullptr, n0, L);
+                }
+                return gf;
+            },
+            [&](const IterSums<T>& S) {
+                if (pre) return a.CtC ? launchGatherIter<true, true>(a, S, nullptr, ctx) : launchGatherIter<false, true>(a, S, nullptr, ctx);
+                double* rr0 = a.first ? iterRR0 : nullptr;
+                const int g = a.CtC ? launchGatherIter<true, false>(a, S, rr0, ctx) : launchGatherIter<false, false>(a, S, rr0, ctx);
+                iterRR0n = a.first ? g : 0;
+                return g;
+            });
+        return true;
+    }
+    // what describe() says about the launch-per-iteration loop ("; key=value ..."): two launches, or the predicate's reason
+    std::string perIterationNote(bool lmv) const override {
+        if (const char* why = fusedWhyNot()) return std::string("; why_not_fused=") + why;
+        char buf[200];
+        snprintf(buf, sizeof buf, "; launches_per_iteration=2; kernels=%s+se_gatherIter<%s, %s, %s>", this->usePreconditioner ? "ge_flatStep" : "ge_flatStepNoPre", sizeof(T) == 4 ? "float" : "double",
+                 E::kName, lmv ? "LM" : "GN");
+        return buf;
+    }
+    std::string describe(int, bool lmv, const OnChipLm<T>*) override { return "path=launch-per-iteration" + perIterationNote(lmv); }
 };
 
 }  // namespace optamd

@@ -387,12 +387,14 @@ struct MarchOps : Base {
             marchCoefficients(coef, ctx);
         }
     }
+    bool marched = false;      // the loop in progress runs on the marching template (decided by its first launch)
     bool pcgIteration(const PcgIterArgs<T>& a, LaunchCtx& ctx) override {
-        if (!useMarch || a.pre || a.CtC) return false;      // Gauss-Newton only: the Levenberg-Marquardt loop keeps the generic kernels
-        if (a.first) produceCoefficients(ctx);
+        // Gauss-Newton without a preconditioner only; every other loop is Base's business (a functor energy: two launches under amd_stencil_fused = 1, else refused -- the generic kernels)
+        if (!useMarch || a.pre || a.CtC) { if (a.first) marched = false; return Base::pcgIteration(a, ctx); }
+        if (a.first) { marched = true; produceCoefficients(ctx); }
         return march.launch(marchOp(), mW, mH, marchFlags, mCus, a, ctx, coef);
     }
-    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return march.finish(delta, (long)Op::C * mW * mH, mCus, ctx); }
+    const T* pcgFinish(T* delta, LaunchCtx& ctx) override { return marched ? march.finish(delta, (long)Op::C * mW * mH, mCus, ctx) : Base::pcgFinish(delta, ctx); }
     bool deltaMovable() const override { return (useMarch || movableWhenOff) && !this->slab.active; }      // (the march takes delta from its arguments at every launch: PcgSolver::deltaTrial)
     // the whole linear solve on chip, X += delta behind a Gauss-Newton one included (onchip_launch.h)
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
@@ -406,7 +408,8 @@ struct MarchOps : Base {
         });
     }
     OnchipGuard* onChipGuard() override { return &oc.guard; }
-    std::string describe(int L, bool lmv, const OnChipLm<T>* lmc) override { return oc.describe(useMarch ? L : 0, lmv, lmc); }
+    // (the loop that is Base's -- Levenberg-Marquardt, or everything with the march switched off -- adds its own note: two launches per PCG iteration or why not)
+    std::string describe(int L, bool lmv, const OnChipLm<T>* lmc) override { return oc.describe(useMarch ? L : 0, lmv, lmc) + (lmv || !useMarch ? this->perIterationNote(lmv) : std::string()); }
 };
 
 }  // namespace

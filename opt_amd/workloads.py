@@ -461,3 +461,31 @@ def spring_from_mesh(V, F, pinned, lifted, double=False, seed=0, perturb=0.0, li
     return Problem("spring_mesh_deformation", (len(V),),
                    [X.astype(ft), V.astype(ft), cons.astype(ft), np.float32(np.sqrt(3.0)), np.float32(np.sqrt(12.0)),
                     np.array(len(heads), dtype=np.int32), heads, tails], (0,), double, {"n_edges": int(len(heads))})
+
+
+VECTOR_TV_T = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "examples", "plugins", "vector_tv_denoising.t"))
+
+
+def vector_tv_denoising(W, H=None, double=False, seed=0, mask=None, noise=0.1, eps=0.1, w_fit=1.0, w_reg=0.5):
+    """examples/plugins/vector_tv_denoising.t (an image-domain energy a plug-in brings; its .t is VECTOR_TV_T): A = a smooth two-channel field of unit amplitude
+    plus `noise`, X = A moved by a further 0.5 `noise` (so the fit residuals do not start at 0), eps at the scale of the neighbour differences (the square root is
+    neither linear nor singular there).  mask: None (every pixel an unknown), "block" (a block in the middle is excluded) or "border" (the first and last row and
+    column are, along every axis that has at least three pixels -- an axis of one pixel has no border of its own)."""
+    H = H or W
+    ft = np.float64 if double else np.float32
+    rng = np.random.default_rng(seed + 11)
+    A = np.stack([_smooth_image(W, H, rng, octaves=3), _smooth_image(W, H, rng, octaves=3)], -1) + rng.normal(0, noise, size=(H, W, 2))
+    X = A + rng.normal(0, 0.5 * noise, size=(H, W, 2))
+    M = np.zeros((H, W))
+    if mask == "block":
+        x0, y0 = W // 3, H // 3
+        M[y0:y0 + max(1, H // 4), x0:x0 + max(1, W // 4)] = 1.0
+    elif mask == "border":
+        if H >= 3:
+            M[0, :] = 1.0; M[-1, :] = 1.0
+        if W >= 3:
+            M[:, 0] = 1.0; M[:, -1] = 1.0
+    else:
+        assert mask is None, mask
+    return Problem("vector_tv_denoising", (W, H), [X.astype(ft), A.astype(ft), M.astype(ft), np.float32(w_fit), np.float32(w_reg), np.float32(eps)], (0,), double,
+                   {"mask": mask})

@@ -36,6 +36,8 @@ inline int devSwitch(const char* name, int dflt) {
         }                                                                                                 \
     } while (0)
 
+#include "dev_buf.h"      // DevBuf<T>: a device buffer that frees itself
+
 namespace optamd {
 
 constexpr int kWave = 64;

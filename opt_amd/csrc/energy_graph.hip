@@ -6,7 +6,7 @@
 // vector with one atomic per (vertex, channel); the per-vertex ("centred") kernel runs first and OVERWRITES,
 // the edge kernel then accumulates on top (solver.t:1032-1036, 1062-1065).
 //
-// MI355X design: no atomics.  The edge lists are turned into per-vertex out- / in-lists once per graph (ensureCsr), and J^T J p is a GATHER:
+// MI355X design: no atomics.  The edge lists are turned into per-vertex out- / in-lists once per graph (graph_lists.h VertexLists; ArapOps::rebuildLists), and J^T J p is a GATHER:
 //   * symmetric graphs whose longest out-list has at most 16 entries (every mesh: OptGraph.h:64-76 emits both directions of every edge; checked per vertex by csr_symmetric):
 //     one walk of a vertex's out-list serves both edge directions.  Round 6 layout: what a half-edge needs of its neighbour lives in 16-byte SoA PLANES (D0 / D1: p and its Angle
 //     part, rewritten every PCG iteration; T0 / T1: sines / cosines; U0: rest position) and the out-lists in ELL order, one lane per vertex (arap_applyEll) -- the gathers of a
@@ -20,7 +20,7 @@
 // and the J^T J p alternative of development builds (-DOPT_AMD_DEV_SWITCHES, OPT_AMD_ARAP_GATHER=0).
 #include "energy.h"
 #include "graph_pcg.h"
-#include <hipcub/hipcub.hpp>
+#include "graph_lists.h"
 #include <cstring>
 
 namespace optamd {
@@ -261,34 +261,6 @@ struct GraphCsr { const int* outOff; const int* outIdx; const int* inOff; const 
 __global__ __launch_bounds__(kBlock) void csr_neighbours(const int* __restrict__ v0, const int* __restrict__ v1, int nE, const int* __restrict__ outIdx, const int* __restrict__ inIdx,
                                                          int* __restrict__ outNbr, int* __restrict__ inNbr) {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nE; k += gridDim.x * blockDim.x) { outNbr[k] = v1[outIdx[k]]; inNbr[k] = v0[inIdx[k]]; }
-}
-
-__global__ __launch_bounds__(kBlock) void csr_count(const int* __restrict__ v0, const int* __restrict__ v1, int nE, int* __restrict__ outDeg, int* __restrict__ inDeg) {
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nE; e += gridDim.x * blockDim.x) { atomicAdd(outDeg + v0[e], 1); atomicAdd(inDeg + v1[e], 1); }
-}
-__global__ __launch_bounds__(kBlock) void csr_fill(const int* __restrict__ v0, const int* __restrict__ v1, int nE, const int* __restrict__ outOff, const int* __restrict__ inOff,
-                                                   int* __restrict__ outCur, int* __restrict__ inCur, int* __restrict__ outIdx, int* __restrict__ inIdx) {
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nE; e += gridDim.x * blockDim.x) {
-        const int a = v0[e], b = v1[e];
-        outIdx[outOff[a] + atomicAdd(outCur + a, 1)] = e;
-        inIdx[inOff[b] + atomicAdd(inCur + b, 1)] = e;
-    }
-}
-__global__ __launch_bounds__(kBlock) void csr_sort(long N, const int* __restrict__ off, int* __restrict__ idx) {   // per-vertex insertion sort: fixed summation order
-    for (long v = blockIdx.x * (long)blockDim.x + threadIdx.x; v < N; v += (long)gridDim.x * blockDim.x) {
-        const int b = off[v], e = off[v + 1];
-        for (int i = b + 1; i < e; ++i) { const int x = idx[i]; int j = i - 1; while (j >= b && idx[j] > x) { idx[j + 1] = idx[j]; --j; } idx[j + 1] = x; }
-    }
-}
-__global__ __launch_bounds__(kBlock) void csr_checksum(const int* __restrict__ v0, const int* __restrict__ v1, int nE, unsigned long long* __restrict__ out) {
-    unsigned long long acc = 0;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nE; e += gridDim.x * blockDim.x)
-        acc += ((unsigned long long)(unsigned)v0[e] * 0x9E3779B97F4A7C15ull + (unsigned long long)(unsigned)v1[e] * 0xC2B2AE3D27D4EB4Full) ^ ((unsigned long long)e * 0x165667B19E3779F9ull);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
-    __shared__ unsigned long long part[kBlock / kWave];      // one atomic per workgroup: 12 000 wave-level atomics on one address took 100 us per bind
-    if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) { unsigned long long t = 0; for (int w = 0; w < kBlock / kWave; ++w) t += part[w]; atomicAdd(out, t); }
 }
 
 // 8 lanes per vertex, each walking one slot of the out-list and one of the in-list (a mesh vertex has ~6 of each), so the
@@ -640,83 +612,47 @@ template <class T>
 struct ArapOps : EnergyOps<T> {
     ArapArgs<T> A{};
     int cus = 256;
-    long dCapacity = 0;
-    // edge lists per vertex for the gather path (rebuilt when the graph arrays change)
-    int *outOff = nullptr, *outIdx = nullptr, *inOff = nullptr, *inIdx = nullptr, *cursors = nullptr; T* Jp = nullptr;
-    void* scanTemp = nullptr; size_t scanTempBytes = 0; unsigned long long* dChecksum = nullptr;
-    const int *csrV0 = nullptr, *csrV1 = nullptr; int csrNE = -1; unsigned long long csrSum = 0; bool csrValid = false;
+    DevBuf<T> D;      // A.D
+    // edge lists per vertex for the gather path (rebuilt when the graph arrays change): out = the half-edges a vertex heads, in = the ones it tails, ids = edge ids
+    VertexLists outList, inList; DevBuf<T> Jp;
     bool useGather = true;   // (development builds: OPT_AMD_ARAP_GATHER=0 scatters with wave-aggregated atomics instead)
-    T* D9 = nullptr; long d9Capacity = 0; int* nbr = nullptr;
+    DevBuf<T> D9; DevBuf<int> nbr;
     // symmetric-graph path (arap_applyEll): 16-byte planes D0, D1 (dynamic), T0, T1, U0 (per Gauss-Newton step) and the out-lists in ELL order; OPT_AMD_ARAP_SYM=0 keeps arap_applyFused
     bool useSym = true, symGraph = false;
     int ellOverflow = 0;      // the longest out-list of a symmetric graph that left the plane path for it (> kEllMax), else 0
-    ArapPlanes<T> planes{}; void* planeMem = nullptr; int* ellMem = nullptr; int* dNotSym = nullptr;
+    ArapPlanes<T> planes{}; DevBuf<Q4<T>> planeMem; DevBuf<int> ellMem, dNotSym;
     bool symPath() const { return useGather && useSym && symGraph; }
-    ~ArapOps() override {
-        if (D9) (void)hipFree(D9);
-        if (nbr) (void)hipFree(nbr);
-        for (void* q : {planeMem, (void*)ellMem, (void*)dNotSym}) if (q) (void)hipFree(q);
-        for (void* q : {(void*)A.D, (void*)outOff, (void*)outIdx, (void*)inOff, (void*)inIdx, (void*)cursors, (void*)Jp, scanTemp, (void*)dChecksum}) if (q) (void)hipFree(q);
-    }
-    void ensureCsr(LaunchCtx& ctx) {
-        hipStream_t st = ctx.stream;
-        if (!dChecksum) HIP_CHECK(hipMalloc((void**)&dChecksum, 8));
-        HIP_CHECK(hipMemsetAsync(dChecksum, 0, 8, st));
+    GraphCsr csr() const { return GraphCsr{outList.off, outList.idx, inList.off, inList.idx, nbr, nbr + std::max(1, A.nE)}; }
+    void rebuildLists(hipStream_t st) {      // both lists, then what ARAP derives from them
         const int ge = edgeGrid(A.nE, cus);
-        csr_checksum<<<ge, kBlock, 0, st>>>(A.v0, A.v1, A.nE, dChecksum);
-        unsigned long long sum = 0;
-        HIP_CHECK(hipMemcpyAsync(&sum, dChecksum, 8, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st));
-        if (csrValid && csrV0 == A.v0 && csrV1 == A.v1 && csrNE == A.nE && csrSum == sum) return;
-        ScopedKernel k(ctx, "buildEdgeLists");
-        for (void* q : {(void*)outOff, (void*)outIdx, (void*)inOff, (void*)inIdx, (void*)cursors, (void*)Jp}) if (q) HIP_CHECK(hipFree(q));
-        const size_t nv = (size_t)A.N + 1;
-        HIP_CHECK(hipMalloc((void**)&outOff, nv * 4)); HIP_CHECK(hipMalloc((void**)&inOff, nv * 4)); HIP_CHECK(hipMalloc((void**)&cursors, 2 * nv * 4));
-        HIP_CHECK(hipMalloc((void**)&outIdx, (size_t)std::max(1, A.nE) * 4)); HIP_CHECK(hipMalloc((void**)&inIdx, (size_t)std::max(1, A.nE) * 4));
-        HIP_CHECK(hipMalloc((void**)&Jp, (size_t)9 * std::max(1, A.nE) * sizeof(T)));       // 6-scalar records of J^T J p, 9-scalar records of J^T F
-        HIP_CHECK(hipMemsetAsync(cursors, 0, 2 * nv * 4, st));
-        int* outDeg = cursors; int* inDeg = cursors + nv;
-        csr_count<<<ge, kBlock, 0, st>>>(A.v0, A.v1, A.nE, outDeg, inDeg);
-        size_t need = 0;
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, outDeg, outOff, (int)nv, st));
-        if (need > scanTempBytes) { if (scanTemp) HIP_CHECK(hipFree(scanTemp)); HIP_CHECK(hipMalloc(&scanTemp, need)); scanTempBytes = need; }
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTemp, need, outDeg, outOff, (int)nv, st));
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTemp, need, inDeg, inOff, (int)nv, st));
-        HIP_CHECK(hipMemsetAsync(cursors, 0, 2 * nv * 4, st));
-        csr_fill<<<ge, kBlock, 0, st>>>(A.v0, A.v1, A.nE, outOff, inOff, outDeg, inDeg, outIdx, inIdx);
-        csr_sort<<<vgrid(), kBlock, 0, st>>>(A.N, outOff, outIdx);
-        csr_sort<<<vgrid(), kBlock, 0, st>>>(A.N, inOff, inIdx);
-        if (nbr) HIP_CHECK(hipFree(nbr));
-        HIP_CHECK(hipMalloc((void**)&nbr, (size_t)2 * std::max(1, A.nE) * 4));
-        csr_neighbours<<<ge, kBlock, 0, st>>>(A.v0, A.v1, A.nE, outIdx, inIdx, nbr, nbr + std::max(1, A.nE));
+        outList.build(SlotIdx<1>{{A.v0}}, A.nE, A.N, cus, st);
+        inList.build(SlotIdx<1>{{A.v1}}, A.nE, A.N, cus, st);
+        Jp.reserve((size_t)9 * std::max(1, A.nE));       // 6-scalar records of J^T J p, 9-scalar records of J^T F
+        nbr.reserve((size_t)2 * std::max(1, A.nE));
+        csr_neighbours<<<ge, kBlock, 0, st>>>(A.v0, A.v1, A.nE, outList.idx, inList.idx, nbr, nbr + std::max(1, A.nE));
         // does every edge come with its reverse (per vertex: out-neighbours == in-neighbours as multisets)?  Then J^T J p walks the out-lists only (arap_applySym)
         symGraph = false; ellOverflow = 0;
-        if (useSym) {
-            if (!dNotSym) HIP_CHECK(hipMalloc((void**)&dNotSym, 4));
-            HIP_CHECK(hipMemsetAsync(dNotSym, 0, 4, st));
-            csr_symmetric<<<vgrid(), kBlock, 0, st>>>(A.N, outOff, nbr, inOff, nbr + std::max(1, A.nE), dNotSym);
-            int bad = 1;
-            HIP_CHECK(hipMemcpyAsync(&bad, dNotSym, 4, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st));
-            symGraph = bad == 0;
-            for (void* q : {planeMem, (void*)ellMem}) if (q) HIP_CHECK(hipFree(q));
-            planeMem = nullptr; ellMem = nullptr; planes = ArapPlanes<T>{};
-            if (symGraph) {      // the longest out-list decides the ELL width; a vertex beyond kEllMax sends the graph to the edge-list gather
-                HIP_CHECK(hipMemsetAsync(dNotSym, 0, 4, st));
-                csr_maxDegree<<<vgrid(), kBlock, 0, st>>>(A.N, outOff, dNotSym);
-                int K = 0;
-                HIP_CHECK(hipMemcpyAsync(&K, dNotSym, 4, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st));
-                if (K > kEllMax) { symGraph = false; ellOverflow = K; }
-                else {
-                    K = std::max(K, 1);
-                    const size_t n = (size_t)std::max<long>(1, A.N);
-                    HIP_CHECK(hipMalloc(&planeMem, 5 * n * sizeof(Q4<T>))); HIP_CHECK(hipMemsetAsync(planeMem, 0, 5 * n * sizeof(Q4<T>), st));
-                    HIP_CHECK(hipMalloc((void**)&ellMem, ((size_t)K + 1) * n * sizeof(int)));
-                    Q4<T>* q = (Q4<T>*)planeMem;
-                    planes = ArapPlanes<T>{q, q + n, q + 2 * n, q + 3 * n, q + 4 * n, ellMem, ellMem + (size_t)K * n, K};
-                    arap_buildEll<<<vgrid(), kBlock, 0, st>>>(A.N, outOff, nbr, K, ellMem, ellMem + (size_t)K * n);
-                }
-            }
-        }
-        csrV0 = A.v0; csrV1 = A.v1; csrNE = A.nE; csrSum = sum; csrValid = true;
+        if (!useSym) return;
+        dNotSym.reserve(1);
+        HIP_CHECK(hipMemsetAsync(dNotSym, 0, 4, st));
+        csr_symmetric<<<vgrid(), kBlock, 0, st>>>(A.N, outList.off, nbr, inList.off, nbr + std::max(1, A.nE), dNotSym);
+        int bad = 1;
+        HIP_CHECK(hipMemcpyAsync(&bad, dNotSym, 4, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st));
+        symGraph = bad == 0;
+        planeMem.release(); ellMem.release(); planes = ArapPlanes<T>{};
+        if (!symGraph) return;
+        // the longest out-list decides the ELL width; a vertex beyond kEllMax sends the graph to the edge-list gather
+        HIP_CHECK(hipMemsetAsync(dNotSym, 0, 4, st));
+        csr_maxDegree<<<vgrid(), kBlock, 0, st>>>(A.N, outList.off, dNotSym);
+        int K = 0;
+        HIP_CHECK(hipMemcpyAsync(&K, dNotSym, 4, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st));
+        if (K > kEllMax) { symGraph = false; ellOverflow = K; return; }
+        K = std::max(K, 1);
+        const size_t n = (size_t)std::max<long>(1, A.N);
+        planeMem.reserveZeroed(5 * n, st); ellMem.reserve(((size_t)K + 1) * n);
+        Q4<T>* q = planeMem;
+        planes = ArapPlanes<T>{q, q + n, q + 2 * n, q + 3 * n, q + 4 * n, ellMem, ellMem + (size_t)K * n, K};
+        arap_buildEll<<<vgrid(), kBlock, 0, st>>>(A.N, outList.off, nbr, K, ellMem, ellMem + (size_t)K * n);
     }
     ArapOps(const unsigned* dims) {
         A.N = dims[0];
@@ -735,13 +671,9 @@ struct ArapOps : EnergyOps<T> {
         A.w_fit = (T) * (const float*)p[0]; A.w_reg = (T) * (const float*)p[1];
         A.Offset = (const T*)p[2]; A.Angle = (const T*)p[3]; A.UrShape = (const T*)p[4]; A.Constraints = (const T*)p[5];
         A.nE = *(const int*)p[6]; A.v0 = (const int*)p[7]; A.v1 = (const int*)p[8];   // Graph("G", 6, "v0", {N}, 7, "v1", {N}, 8)
-        if (A.nE > dCapacity) {
-            if (A.D) HIP_CHECK(hipFree(A.D));
-            dCapacity = A.nE;
-            HIP_CHECK(hipMalloc((void**)&A.D, (size_t)9 * dCapacity * sizeof(T)));
-            HIP_CHECK(hipMemset(A.D, 0, (size_t)9 * dCapacity * sizeof(T)));
-        }
-        if (useGather) ensureCsr(ctx);      // (UrShape is an input of the solve: arap_buildStatic reads it afresh in every Gauss-Newton step)
+        D.reserveZeroed((size_t)9 * std::max(0, A.nE), ctx.stream); A.D = D;
+        // one change decision for the pair of lists: `outList` keeps the signature over both arrays
+        if (useGather) outList.ensureBy(SlotIdx<2>{{A.v0, A.v1}}, A.nE, A.N, cus, ctx, "buildEdgeLists", [&] { rebuildLists(ctx.stream); });      // (UrShape is an input of the solve: arap_buildStatic reads it afresh in every Gauss-Newton step)
     }
     T* unknownPtr(int img) const override { return const_cast<T*>(img == 0 ? A.Offset : A.Angle); }
     int vgrid() const { static const int cap = getenv("OPT_AMD_ARAP_VGRID") ? atoi(getenv("OPT_AMD_ARAP_VGRID")) : kMaxPartials / 2; return (int)std::max<long>(1, std::min<long>((A.N + kBlock - 1) / kBlock, cap)); }
@@ -754,7 +686,7 @@ struct ArapOps : EnergyOps<T> {
     void evalJTF(T* r, T* diag, LaunchCtx& ctx) override {
         { ScopedKernel k(ctx, "PCGInit1"); arap_vertices<T, 2><<<vgrid(), kBlock, 0, ctx.stream>>>(A, nullptr, r, diag, nullptr, nullptr); }
         if (useGather) {
-            GraphCsr G{outOff, outIdx, inOff, inIdx};
+            const GraphCsr G = csr();
             { ScopedKernel k(ctx, "PCGInit1_Graph"); arap_edgeJTF<T><<<edgeGrid(A.nE, cus), kBlock, 0, ctx.stream>>>(A, Jp); }
             { ScopedKernel k(ctx, "PCGInit1_Gather"); arap_vertexGatherJTF<T><<<vgrid(), kBlock, 0, ctx.stream>>>(A, G, Jp, r, diag); }
             if (symPath()) {    // the sines / cosines of this Gauss-Newton iteration's angles and the rest positions as planes, for arap_applyEll
@@ -762,7 +694,7 @@ struct ArapOps : EnergyOps<T> {
                 arap_buildStatic<T><<<vgrid(), kBlock, 0, ctx.stream>>>(A, planes);
             }
             if (!symPath()) {     // the derivative columns of this Gauss-Newton iteration as 36-byte rows for arap_applyFused
-                if (A.nE > d9Capacity) { if (D9) HIP_CHECK(hipFree(D9)); d9Capacity = A.nE; HIP_CHECK(hipMalloc((void**)&D9, (size_t)9 * std::max<long>(1, d9Capacity) * sizeof(T))); }
+                D9.reserve((size_t)9 * std::max(0, A.nE));
                 ScopedKernel k(ctx, "packDerivativeRows");
                 arap_packD<T><<<edgeGrid(A.nE, cus), kBlock, 0, ctx.stream>>>(A.D, D9, (long)A.nE);
             }
@@ -777,7 +709,7 @@ struct ArapOps : EnergyOps<T> {
             return;
         }
         if (useGather) {
-            GraphCsr G{outOff, outIdx, inOff, inIdx, nbr, nbr + std::max(1, A.nE)};
+            const GraphCsr G = csr();
             ScopedKernel k(ctx, "PCGStep1");
             arap_applyFused<T><<<gv, kBlock, 0, ctx.stream>>>(A, G, D9, v, out, CtC, dot ? dot->partials : nullptr);
             if (dot) dot->n = gv;
@@ -851,12 +783,7 @@ struct ArapOps : EnergyOps<T> {
         for (const AoVariant& v : aoVariants<T>())
             for (int m = 0; m < 2; ++m) {
                 const void* fn = m ? v.lm : v.gn;
-                if (!fn) continue;
-                const size_t lds = (size_t)v.v * kAoMaxBlock * v.ldsPerVertex;
-                hipFuncAttributes fa{};
-                if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.localSizeBytes != 0) { (void)hipGetLastError(); continue; }      // (no scratch in a kernel that is all latency)
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); continue; }      // (a variant the device cannot hold is not offered)
-                aoOffers[m].push_back({v.v, fn, v.ldsPerVertex});
+                if (ocOfferable(fn, (size_t)v.v * kAoMaxBlock * v.ldsPerVertex)) aoOffers[m].push_back({v.v, fn, v.ldsPerVertex});      // (a variant the device cannot hold is not offered)
             }
     }
     long aoMaxVertices(bool lmv) { aoInit(); return aoOffers[lmv].empty() ? 0 : (long)aoOffers[lmv].back().v * kAoMaxBlock; }
@@ -880,14 +807,7 @@ struct ArapOps : EnergyOps<T> {
         const int threads = std::max(1, divUp(divUp(A.N, o->v), kWave)) * kWave;      // only the waves the vertex count needs
         ArapOcArgs<T> K{A, planes, r0, p0, this->onChipPre, delta, L, traceDev, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0), lm ? lm->resetPeriod : 0, lm ? lm->breakInfo : nullptr};
         void* kargs[] = {(void*)&K};
-        ocGuard.allocWords(ctx.stream);
-        {
-            ScopedKernel k(ctx, "PCGSolveOnChip");
-            if (hipLaunchKernel(o->fn, dim3(1), dim3(threads), kargs, (size_t)threads * o->v * o->lds, ctx.stream) != hipSuccess) { (void)hipGetLastError(); ocGuard.enabled = false; return false; }
-        }
-        if (!lm) ocApplyDeltaToUnknowns(*this, delta, 64, ocGuard, ctx);      // PCGLinearUpdate X += delta, guarded (LM: the solver applies the update itself)
-        ocGuard.launched = true;
-        return true;
+        return ocLaunchSolve(o->fn, dim3(1), dim3(threads), kargs, (size_t)threads * o->v * o->lds, ocGuard, *this, delta, lm != nullptr, ctx);
     }
     OnchipGuard* onChipGuard() override { return &ocGuard; }
     std::string describe(int L, bool lmv, const OnChipLm<T>* lm) override {      // ("key=value; ..." -- no ';' inside a value)
@@ -911,7 +831,7 @@ struct ArapOps : EnergyOps<T> {
 // and the parameter slots are those of the volumetric .t re-ordered into ARAP's.  The lattice graph is symmetric (six neighbours), so J^T J p runs on the plane gather (arap_applyEll).
 template <class T>
 struct VolumetricArapOps : ArapOps<T> {
-    int* dv0 = nullptr; int* dv1 = nullptr; int nEdges = 0;
+    DevBuf<int> dv0, dv1; int nEdges = 0;
     static const unsigned* count(const unsigned* dims) { static thread_local unsigned n[1]; n[0] = dims[0] * dims[1] * dims[2]; return n; }
     explicit VolumetricArapOps(const unsigned* dims) : ArapOps<T>(count(dims)) {
         const int W = (int)dims[0], H = (int)dims[1], D = (int)dims[2];
@@ -927,12 +847,11 @@ struct VolumetricArapOps : ArapOps<T> {
             }
         }
         nEdges = (int)v0.size();
-        HIP_CHECK(hipMalloc((void**)&dv0, std::max<size_t>(1, v0.size()) * sizeof(int))); HIP_CHECK(hipMalloc((void**)&dv1, std::max<size_t>(1, v1.size()) * sizeof(int)));
+        dv0.reserve(std::max<size_t>(1, v0.size())); dv1.reserve(std::max<size_t>(1, v1.size()));
         HIP_CHECK(hipMemcpy(dv0, v0.data(), v0.size() * sizeof(int), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv1, v1.data(), v1.size() * sizeof(int), hipMemcpyHostToDevice));
     }
-    ~VolumetricArapOps() override { (void)hipFree(dv0); (void)hipFree(dv1); }
     void bind(void** p, LaunchCtx& ctx) override {      // volumetric: Offset, Angle, UrShape, Constraints, w_fitSqrt, w_regSqrt  ->  ARAP: w_fit, w_reg, Offset, Angle, UrShape, Constraints, |E|, v0, v1
-        void* q[9] = {p[4], p[5], p[0], p[1], p[2], p[3], &nEdges, dv0, dv1};
+        void* q[9] = {p[4], p[5], p[0], p[1], p[2], p[3], &nEdges, dv0.p, dv1.p};
         ArapOps<T>::bind(q, ctx);
     }
 };

@@ -6,7 +6,7 @@
 //   edge pass (one thread per hyperedge): S = Dual<T, V*K (+1)> over the V vertices of the edge; its J^T (J p) contributions go into one
 //                K-scalar record per (hyperedge, slot),
 //   vertex pass (one thread per vertex): the contribution of the vertex's own residuals (+ CtC p) plus the records of every (hyperedge, slot)
-//                the vertex occupies, in ascending (slot, hyperedge) order from incidence lists built once per graph by a counting sort.
+//                the vertex occupies, in ascending (slot, hyperedge) order from incidence lists built once per graph by a counting sort (graph_lists.h VertexLists).
 // No atomics: unlike the reference's graph kernels (one atomic per (vertex, unknown), unordered) a solve is bit-reproducible.
 // OPT_AMD_GRAPH_GATHER=0 selects the scatter formulation instead (wave-aggregated atomics for the first vertex, whose edges arrive
 // grouped, OptGraph.h:64-76; plain atomics for the others).
@@ -21,7 +21,7 @@
 #include "graph_pcg.h"
 #include "onchip_sync.h"
 #include "graph_partition.h"
-#include <hipcub/hipcub.hpp>
+#include "graph_lists.h"      // VertexLists: the incidence lists, built once per graph
 
 namespace optamd {
 
@@ -55,35 +55,8 @@ struct EdgeCtx {
     }
 };
 
-// ---- incidence lists: for every vertex the ids j * nE + e of the (hyperedge e, slot j) pairs it occupies, ascending ----------------------
-template <int V> struct SlotIdx { const int* p[V]; };
+// ---- incidence lists: for every vertex the ids j * nE + e of the (hyperedge e, slot j) pairs it occupies, ascending (graph_lists.h VertexLists) ----
 struct Incidence { const int* off; const int* idx; };       // off == nullptr: scatter mode
-template <int V>
-__global__ __launch_bounds__(kBlock) void inc_count(SlotIdx<V> vi, int nE, int* __restrict__ deg, unsigned long long* __restrict__ checksum) {
-    unsigned long long acc = 0;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nE; e += gridDim.x * blockDim.x)
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const int v = vi.p[j][e];
-            if (deg) atomicAdd(deg + v, 1);
-            acc += ((unsigned long long)(unsigned)v * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)(j * (long)nE + e) * 0x165667B19E3779F9ull);
-        }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
-    if (checksum && (threadIdx.x & (kWave - 1)) == 0) atomicAdd(checksum, acc);     // integer sum: order-independent
-}
-template <int V>
-__global__ __launch_bounds__(kBlock) void inc_fill(SlotIdx<V> vi, int nE, const int* __restrict__ off, int* __restrict__ cur, int* __restrict__ idx) {
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nE; e += gridDim.x * blockDim.x)
-#pragma unroll
-        for (int j = 0; j < V; ++j) { const int v = vi.p[j][e]; idx[off[v] + atomicAdd(cur + v, 1)] = j * nE + e; }
-}
-template <int V>
-__global__ __launch_bounds__(kBlock) void inc_sort(long N, const int* __restrict__ off, int* __restrict__ idx) {   // per-vertex insertion sort: fixed summation order
-    for (long v = blockIdx.x * (long)blockDim.x + threadIdx.x; v < N; v += (long)gridDim.x * blockDim.x) {
-        const int b = off[v], e = off[v + 1];
-        for (int i = b + 1; i < e; ++i) { const int x = idx[i]; int j = i - 1; while (j >= b && idx[j] > x) { idx[j + 1] = idx[j]; --j; } idx[j + 1] = x; }
-    }
-}
 
 // MODE 0: cost, 1: model cost (vec = delta), 2: J^T F + diag, 3: J^T J vec.  LANES > 1 (gather mode): LANES adjacent lanes share one vertex;
 // lane 0 evaluates the vertex's own residuals, every lane walks every LANES-th record of the incidence list, and the partial sums are
@@ -353,44 +326,19 @@ struct GraphOps : EnergyOps<T> {
     int vgrid(int lanes = 1) const { return (int)std::max<long>(1, std::min<long>((g.N * lanes + kBlock - 1) / kBlock, kMaxPartials / 2)); }
     // gather mode state: incidence lists (rebuilt when the graph arrays change: pointers, count or an order-independent checksum) and the record buffer
     bool useGather = true, gatherTooLarge = false;
-    int *incOff = nullptr, *incIdx = nullptr, *cursors = nullptr; T* rec = nullptr; long recCapacity = 0;
-    void* scanTemp = nullptr; size_t scanTempBytes = 0; unsigned long long* dChecksum = nullptr;
-    const int* incV[G::V] = {}; int incNE = -1; unsigned long long incSum = 0; bool incValid = false;
-    ~GraphOps() override { for (void* q : {(void*)incOff, (void*)incIdx, (void*)cursors, (void*)rec, scanTemp, (void*)dChecksum, (void*)ggParts, (void*)ggLists, (void*)ggRec}) if (q) (void)hipFree(q); }
-    Incidence incidence() const { return useGather ? Incidence{incOff, incIdx} : Incidence{nullptr, nullptr}; }
-    void ensureIncidence(LaunchCtx& ctx) {
-        hipStream_t st = ctx.stream;
-        SlotIdx<G::V> vi; bool same = incValid && incNE == g.nE;
-        for (int j = 0; j < G::V; ++j) { vi.p[j] = g.vidx[j]; same = same && incV[j] == g.vidx[j]; }
-        if (!dChecksum) HIP_CHECK(hipMalloc((void**)&dChecksum, 8));
-        HIP_CHECK(hipMemsetAsync(dChecksum, 0, 8, st));
-        const int ge = edgeGrid(g.nE, cus);
-        inc_count<G::V><<<ge, kBlock, 0, st>>>(vi, g.nE, nullptr, dChecksum);
-        unsigned long long sum = 0;
-        HIP_CHECK(hipMemcpyAsync(&sum, dChecksum, 8, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st));
-        if (same && sum == incSum) return;
-        ScopedKernel k(ctx, "buildIncidenceLists");
-        for (void* q : {(void*)incOff, (void*)incIdx, (void*)cursors}) if (q) HIP_CHECK(hipFree(q));
-        const size_t nv = (size_t)g.N + 1, nInc = (size_t)std::max(1, g.nE) * G::V;
-        HIP_CHECK(hipMalloc((void**)&incOff, nv * 4)); HIP_CHECK(hipMalloc((void**)&cursors, nv * 4)); HIP_CHECK(hipMalloc((void**)&incIdx, nInc * 4));
-        if ((long)nInc > recCapacity) { if (rec) HIP_CHECK(hipFree(rec)); HIP_CHECK(hipMalloc((void**)&rec, nInc * 2 * G::K * sizeof(T))); recCapacity = (long)nInc; }
-        HIP_CHECK(hipMemsetAsync(cursors, 0, nv * 4, st));
-        inc_count<G::V><<<ge, kBlock, 0, st>>>(vi, g.nE, cursors, nullptr);
-        size_t need = 0;
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, cursors, incOff, (int)nv, st));
-        if (need > scanTempBytes) { if (scanTemp) HIP_CHECK(hipFree(scanTemp)); HIP_CHECK(hipMalloc(&scanTemp, need)); scanTempBytes = need; }
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTemp, need, cursors, incOff, (int)nv, st));
-        HIP_CHECK(hipMemsetAsync(cursors, 0, nv * 4, st));
-        inc_fill<G::V><<<ge, kBlock, 0, st>>>(vi, g.nE, incOff, cursors, incIdx);
-        inc_sort<G::V><<<vgrid(), kBlock, 0, st>>>(g.N, incOff, incIdx);
-        for (int j = 0; j < G::V; ++j) incV[j] = g.vidx[j];
-        incNE = g.nE; incSum = sum; incValid = true;
+    VertexLists inc; DevBuf<T> rec;      // rec: 2 K scalars per incidence (J^T F and diag; J^T J p uses K of them)
+    Incidence incidence() const { return useGather ? Incidence{inc.off, inc.idx} : Incidence{nullptr, nullptr}; }
+    void ensureLists(LaunchCtx& ctx) {
+        SlotIdx<G::V> vi;
+        for (int j = 0; j < G::V; ++j) vi.p[j] = g.vidx[j];
+        if (!inc.ensure(vi, g.nE, g.N, cus, ctx, "buildIncidenceLists")) return;
+        rec.reserve((size_t)std::max(1, g.nE) * G::V * 2 * G::K);
         ggBuiltG = 0;      // (the partition of amd_onchip = 7 follows the incidence lists)
     }
     void bind(void** p, LaunchCtx& ctx) override {
         g.bindParams(p);
         if (useGather && (long)g.nE * G::V > 0x7fffffffL) { useGather = false; gatherTooLarge = true; }      // incidence ids j * nE + e are 32-bit: beyond that, scatter
-        if (useGather) ensureIncidence(ctx);
+        if (useGather) ensureLists(ctx);
     }
     T* unknownPtr(int img) const override { return const_cast<T*>(g.X[img]); }
     void evalCost(Reduction& out, LaunchCtx& ctx) override {
@@ -426,11 +374,7 @@ struct GraphOps : EnergyOps<T> {
         const long nPad = (this->nScalars + 3) / 4 * 4;      // the solver's vectors (zero beyond nScalars)
         const int gf = flatGrid(nPad, cus, kMaxPartials / 2);
         pcgTwoLaunchIteration(a, nPad, ctx, [] {},
-            [&](bool lm, const LmStep<T>& L) {
-                (lm ? ge_flatStep<T, true> : ge_flatStep<T, false>)<<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
-                    a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L);
-                return gf;
-            },
+            [&](bool lm, const LmStep<T>& L) { return launchFlatStep<false>(a, nPad, gf, lm, L, nullptr, 0, ctx.stream); },
             [&](const IterSums<T>& S) { return launchGather(a.pNew, a.ApNew, a.CtC, a.aDen->partials, S, ctx); });
         return true;
     }
@@ -456,12 +400,8 @@ struct GraphOps : EnergyOps<T> {
         for (const GeOcVariant& v : geOcVariants<T, G>())
             for (int m = 0; m < 2; ++m) {
                 const void* fn = m ? v.lm : v.gn;
-                if (!fn) continue;
-                hipFuncAttributes fa{};
-                if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.localSizeBytes != 0) { (void)hipGetLastError(); continue; }      // (no scratch in a kernel that is all latency)
                 if ((size_t)v.v * kOcWgMaxBlock * kOcLdsPerVertex > kOcLdsBudget) continue;      // (a variant whose largest mesh the CU cannot hold is not offered)
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOcLdsBudget) != hipSuccess) { (void)hipGetLastError(); continue; }
-                ocOffers[m].push_back({v.v, fn});
+                if (ocOfferable(fn, kOcLdsBudget)) ocOffers[m].push_back({v.v, fn});
             }
     }
     long ocMaxVertices(bool lmv) { ocInit(); return ocOffers[lmv].empty() ? 0 : (long)ocOffers[lmv].back().v * kOcWgMaxBlock; }
@@ -487,9 +427,9 @@ struct GraphOps : EnergyOps<T> {
     }
     // ---- ... or as ONE persistent launch of several workgroups (graph_onchip_grid.h; solver parameter amd_onchip = 7, amd_onchip_workgroups) ----
     GraphPartition ggPart;            // the partition in force (host copy: describe() reports from it)
-    int ggBuiltG = 0;                 // its workgroup count; 0: none (the graph has changed: ensureIncidence)
-    GeGridPart* ggParts = nullptr; int* ggLists = nullptr; size_t ggListCap = 0;
-    T* ggRec = nullptr; long ggRecCap = 0;      // the workgroups' record slabs (K scalars per evaluated (hyperedge, slot)), used where the records do not fit LDS
+    int ggBuiltG = 0;                 // its workgroup count; 0: none (the graph has changed: ensureLists)
+    DevBuf<GeGridPart> ggParts; DevBuf<int> ggLists;
+    DevBuf<T> ggRec;      // the workgroups' record slabs (K scalars per evaluated (hyperedge, slot)), used where the records do not fit LDS
     oc_u64 *ggSlots = nullptr, *ggBox = nullptr; long ggBoxWords = 0, ggBoxCap = 0;
     const void* ggFn[2] = {nullptr, nullptr}; bool ggReady = false;
     static constexpr size_t kGgLdsPerVertex = 4 * G::K * sizeof(T);      // p, delta, r, A p
@@ -511,13 +451,8 @@ struct GraphOps : EnergyOps<T> {
         if (ggReady) return;
         ggReady = true;
         const GeGridKernels ks = geGridKernels<T, G>();
-        for (int m = 0; m < 2; ++m) {
-            const void* fn = m ? ks.lm : ks.gn;
-            hipFuncAttributes fa{};
-            if (!fn || hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.localSizeBytes != 0) { (void)hipGetLastError(); continue; }      // (no scratch in a kernel that is all latency)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGgLdsBudget) != hipSuccess) { (void)hipGetLastError(); continue; }
-            ggFn[m] = fn;
-        }
+        for (int m = 0; m < 2; ++m)
+            if (const void* fn = m ? ks.lm : ks.gn; ocOfferable(fn, kGgLdsBudget)) ggFn[m] = fn;
     }
     // the partition for G workgroups on the graph as bound, on the device (blocking copies: once per graph and workgroup count)
     void ggEnsure(int G_) {
@@ -550,9 +485,7 @@ struct GraphOps : EnergyOps<T> {
         }
         lists.push_back(0);      // (never empty)
         HIP_CHECK(hipDeviceSynchronize());      // (no launch still reads the lists about to be replaced)
-        if (lists.size() > ggListCap) { if (ggLists) HIP_CHECK(hipFree(ggLists)); ggListCap = lists.size(); HIP_CHECK(hipMalloc((void**)&ggLists, ggListCap * sizeof(int))); }
-        if (!ggParts) HIP_CHECK(hipMalloc((void**)&ggParts, kGeGridMaxG * sizeof(GeGridPart)));
-        if (recBase > ggRecCap) { if (ggRec) HIP_CHECK(hipFree(ggRec)); ggRecCap = recBase; HIP_CHECK(hipMalloc((void**)&ggRec, (size_t)ggRecCap * G::K * sizeof(T))); }
+        ggLists.reserve(lists.size()); ggParts.reserve(kGeGridMaxG); ggRec.reserve((size_t)recBase * G::K);
         HIP_CHECK(hipMemcpy(ggLists, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(ggParts, parts.data(), parts.size() * sizeof(GeGridPart), hipMemcpyHostToDevice));
         // the tagged words, allocated once per plan: the sums' slots, and the wires' box at its worst case -- every unknown on a wire (a fresh buffer starts cleared: zero is no tag)
@@ -575,7 +508,7 @@ struct GraphOps : EnergyOps<T> {
     // THE predicate of the several-workgroup path: nullptr (on chip with G_ workgroups, the partition built) or why not.  pcgSolveOnChip and describe() both ask here.
     const char* ggWhyNot(int L, bool lmv, const OnChipLm<T>* lm, int G_) {
         if (const char* why = ocCommonWhyNot(L, lmv, lm)) return why;
-        if (!incValid) return "no graph bound yet";
+        if (!inc.valid) return "no graph bound yet";
         if (this->nScalars > 0x7fffffffL / 2) return "too many unknowns";
         ggInit();
         if (!ggFn[lmv]) return "the kernel is not offered on this device (scratch)";
@@ -599,13 +532,7 @@ struct GraphOps : EnergyOps<T> {
         A.tag0 = ocGuard.tags((unsigned)phases, ctx.stream); A.bad = ocGuard.bad; A.firstTicks = tmo.first; A.laterTicks = tmo.later; A.failAt = ocGuard.failAtThisLaunch();
         A.hostErr = lm ? ocGuard.hostErr : nullptr;
         void* kargs[] = {(void*)&A};
-        {
-            ScopedKernel k(ctx, "PCGSolveOnChip");
-            if (hipLaunchKernel(ggFn[lm ? 1 : 0], dim3(G_), dim3(kOcWgMaxBlock), kargs, lds, ctx.stream) != hipSuccess) { (void)hipGetLastError(); ocGuard.enabled = false; return false; }
-        }
-        if (!lm) ocApplyDeltaToUnknowns(*this, delta, 64, ocGuard, ctx);      // PCGLinearUpdate X += delta, guarded (LM: the solver applies the update itself)
-        ocGuard.launched = true;
-        return true;
+        return ocLaunchSolve(ggFn[lm ? 1 : 0], dim3(G_), dim3(kOcWgMaxBlock), kargs, lds, ocGuard, *this, delta, lm != nullptr, ctx);
     }
     bool pcgSolveOnChip(const T* r0, const T* p0, T* delta, int L, double* traceDev, const OnChipLm<T>* lm, LaunchCtx& ctx) override {
         if (const int G_ = ggWanted(); G_ > 1) {
@@ -620,14 +547,7 @@ struct GraphOps : EnergyOps<T> {
         GeOcArgs<T, G> K{g, vo, this->nScalars, incidence(), rec, recInLds ? 1 : 0, r0, p0, this->onChipPre, delta, L, traceDev, lm ? lm->CtC : nullptr, lm ? lm->qTolerance : T(0), lm ? lm->resetPeriod : 0,
                          lm ? lm->breakInfo : nullptr};
         void* kargs[] = {(void*)&K};
-        ocGuard.allocWords(ctx.stream);
-        {
-            ScopedKernel k(ctx, "PCGSolveOnChip");
-            if (hipLaunchKernel(o->fn, dim3(1), dim3(threads), kargs, lds, ctx.stream) != hipSuccess) { (void)hipGetLastError(); ocGuard.enabled = false; return false; }
-        }
-        if (!lm) ocApplyDeltaToUnknowns(*this, delta, 64, ocGuard, ctx);      // PCGLinearUpdate X += delta, guarded (LM: the solver applies the update itself)
-        ocGuard.launched = true;
-        return true;
+        return ocLaunchSolve(o->fn, dim3(1), dim3(threads), kargs, lds, ocGuard, *this, delta, lm != nullptr, ctx);
     }
     OnchipGuard* onChipGuard() override { return &ocGuard; }
     // ("key=value; ..." -- no ';' inside a value.)  At level 7 with more than one workgroup asked for, the answer needs the partition: the first call for a graph and

@@ -2,7 +2,7 @@
 // the body of the walk is arap_half_edge_pair.inc), the argument structs, the term and the store of the sums of a two-launch iteration (arap_applyEll, ge_gather,
 // arap_onchipPcg), LM's extras of the flat PCGStep2 + PCGStep3 pass (arap_flatStepPlanes, ge_flatStep; its scalars are graph_flat_scalars.inc) and the host side of
 // such an iteration (ArapOps::pcgIteration, GraphOps::pcgIteration, StencilOps::pcgIteration) -- and, at the end of the file, the two energy-independent kernels of
-// that pass themselves, ge_flatStep and ge_flatStepNoPre, which both functor engines launch (graph_engine.h, stencil_engine.h).  Every device piece is a force-inlined
+// that pass themselves, ge_flatStep and ge_flatStepNoPre, which both functor engines launch (graph_engine.h, stencil_engine.h) through launchFlatStep.  Every device piece is a force-inlined
 // function on plain values; a kernel keeps its own loop, layout,
 // grid and walk order, and the order in which it adds the terms it gets from here.  No pragma in this file: it is compiled with the contraction setting of the file
 // that includes it (energy_graph_functors.hip and plug-in sources: off; energy_functors.hip: the compiler's default).  The kernels take LmStep, a type of this file's
@@ -165,5 +165,21 @@ __global__ __launch_bounds__(kBlock) void ge_flatStepNoPre(long n, T* __restrict
         if (threadIdx.x == 0) { if (L.qTag) storeTaggedPartial(L.q, blockIdx.x, tq, L.qTag); else L.q[blockIdx.x] = tq; }
     }
 }
+
+namespace {
+// The launch of the flat pass from the arguments of an iteration (the flat(lm, L) of pcgTwoLaunchIteration): ge_flatStep, or for an energy that does not
+// precondition (a.pre == nullptr) ge_flatStepNoPre with the first launch's sum r_0^2 (rr0, nrr0: see there).  Returns the grid.  NOPRE = false: the caller never
+// comes without a preconditioner (GraphOps::pcgIteration), and its translation unit does not instantiate ge_flatStepNoPre.
+template <bool NOPRE, class T>
+int launchFlatStep(const PcgIterArgs<T>& a, long nPad, int grid, bool lm, const LmStep<T>& L, const double* rr0, int nrr0, hipStream_t s) {
+    if (a.pre)
+        (lm ? ge_flatStep<T, true> : ge_flatStep<T, false>)<<<grid, kBlock, 0, s>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
+            a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L);
+    else if constexpr (NOPRE)
+        (lm ? ge_flatStepNoPre<T, true> : ge_flatStepNoPre<T, false>)<<<grid, kBlock, 0, s>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
+            a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, rr0, nrr0, L);
+    return grid;
+}
+}  // namespace
 
 }  // namespace optamd

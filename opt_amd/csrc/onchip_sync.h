@@ -7,7 +7,8 @@
 // The protocol of one phase of a wave-tiled kernel is here as functions: the grid-wide sum with its one bounded wait (ocGridSum), the q early-out (ocZetaBreak), alpha and
 // beta from the totals (ocAlpha, ocBeta).  march_onchipPcg is built from them; sfs_onchipPcg keeps its own text of the same steps (it runs at the cap of the scalar
 // registers and measurably loses with them, see sfs_onchip.h) and shares the small helpers; image_warping's kernels (two-level tree, rank hop, hand-over inside the
-// workgroup) keep their own.
+// workgroup) keep their own.  At the end of the file, the host side the dynamic-LDS solves of the graph kernel sets share: which variants a device offers (ocOfferable), the
+// launch with the guarded update behind it (ocLaunchSolve, ocApplyDeltaToUnknowns).
 #pragma once
 #include "common.h"
 #include <utility>
@@ -322,6 +323,29 @@ void ocApplyDeltaToUnknowns(const Ops& ops, const T* delta, long cap, const Onch
         const int grid = (int)std::max<long>(1, std::min<long>((cnt + kBlock - 1) / kBlock, cap));
         ocApplyDelta<T><<<grid, kBlock, 0, ctx.stream>>>(ops.unknownPtr((int)i), delta + u.offset, cnt, guard.bad, guard.hostErr);
     }
+}
+
+// ---- host side of the dynamic-LDS on-chip solves of the graph kernel sets (arap_onchipPcg, ge_onchipPcg, ge_onchipPcgGrid; the wave-tiled families: onchip_launch.h) ----
+// Is the variant `fn` offered on this device?  It uses no scratch (a kernel that is all latency) and the device grants it maxDynamicLdsBytes of dynamic LDS.
+inline bool ocOfferable(const void* fn, size_t maxDynamicLdsBytes) {
+    hipFuncAttributes fa{};
+    if (fn && hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.localSizeBytes == 0 &&
+        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxDynamicLdsBytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+// The launch of such a solve and what follows it: behind a Gauss-Newton solve the guarded PCGLinearUpdate X += delta over the unknowns of `ops` (LM: the solver applies
+// the update itself).  false: the launch was refused -- the path is switched off.
+template <class T, class Ops>
+bool ocLaunchSolve(const void* fn, dim3 grid, dim3 block, void** kargs, size_t ldsBytes, OnchipGuard& guard, const Ops& ops, const T* delta, bool lm, LaunchCtx& ctx) {
+    guard.allocWords(ctx.stream);
+    {
+        ScopedKernel k(ctx, "PCGSolveOnChip");
+        if (hipLaunchKernel(fn, grid, block, kargs, ldsBytes, ctx.stream) != hipSuccess) { (void)hipGetLastError(); guard.enabled = false; return false; }
+    }
+    if (!lm) ocApplyDeltaToUnknowns(ops, delta, 64, guard, ctx);
+    guard.launched = true;
+    return true;
 }
 
 }  // namespace

@@ -283,9 +283,9 @@ struct StencilOps : EnergyOps<T> {
         const long n = (long)e.W * e.H * e.D;
         for (int i = 0; i < E::NIMG; ++i) { vo.o[i] = this->nScalars; this->addUnknown(E::unknownParam(i), n, E::channels(i)); }
         int dev = 0; HIP_CHECK(hipGetDevice(&dev)); HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if constexpr (E::NAUX > 0) { HIP_CHECK(hipMalloc((void**)&e.aux, (size_t)E::NAUX * n * sizeof(T))); HIP_CHECK(hipMemset(e.aux, 0, (size_t)E::NAUX * n * sizeof(T))); }
+        if constexpr (E::NAUX > 0) { aux.reserveZeroed((size_t)E::NAUX * n, nullptr); HIP_CHECK(hipStreamSynchronize(nullptr)); e.aux = aux.p; }
     }
-    ~StencilOps() override { if constexpr (E::NAUX > 0) (void)hipFree(e.aux); if (iterRR0) (void)hipFree(iterRR0); }
+    DevBuf<T> aux;      // the functor's ComputedArrays planes (E::NAUX > 0); the functor keeps the raw pointer
     void precompute(LaunchCtx& ctx) override {
         if constexpr (E::NAUX > 0) { ScopedKernel k(ctx, "precompute"); se_precompute<T, E><<<grid(), kBlock, 0, ctx.stream>>>(e); }
     }
@@ -313,7 +313,7 @@ struct StencilOps : EnergyOps<T> {
         if (lmWithoutBOrQ) return "Levenberg-Marquardt without b or q";
         return nullptr;
     }
-    double* iterRR0 = nullptr;       // PRE = false: sum r_0^2 of the first launch of a linear solve, one partial per workgroup (kMaxPartials doubles) ...
+    DevBuf<double> iterRR0;          // PRE = false: sum r_0^2 of the first launch of a linear solve, one partial per workgroup (kMaxPartials doubles) ...
     int iterRR0n = 0;                // ... how many, until the flat pass behind that launch has been given them (0: none pending)
     template <bool LM, bool PRE>
     int launchGatherIter(const PcgIterArgs<T>& a, const IterSums<T>& S, double* rr0, LaunchCtx& ctx) {
@@ -326,22 +326,15 @@ struct StencilOps : EnergyOps<T> {
         const long nPad = (this->nScalars + 3) / 4 * 4;      // the solver's vectors (zero beyond nScalars)
         const int gf = flatGrid(nPad, cus, kMaxPartials / 2);
         const bool pre = a.pre != nullptr;
-        if (!pre && !iterRR0) HIP_CHECK(hipMalloc((void**)&iterRR0, kMaxPartials * sizeof(double)));
+        if (!pre) iterRR0.reserve(kMaxPartials);
         pcgTwoLaunchIteration(a, nPad, ctx, [] {},
-            [&](bool lm, const LmStep<T>& L) {
-                if (pre)
-                    (lm ? ge_flatStep<T, true> : ge_flatStep<T, false>)<<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.pre, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
-                        a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, L);
-                else {      // (the pass behind the first launch of the solve: beta's expansion starts from sum r_0^2, which is not the alphaNumerator there)
-                    const int n0 = a.afterReset ? 0 : iterRR0n;
-                    (lm ? ge_flatStepNoPre<T, true> : ge_flatStepNoPre<T, false>)<<<gf, kBlock, 0, ctx.stream>>>(nPad, a.delta, a.pOld, a.rOld, a.ApOld, a.rNew, a.pNew, a.aNumPrev.partials, a.aNumPrev.n,
-                        a.aDenPrev.partials, a.aDenPrev.n, a.s2Prev.partials, a.s2Prev.n, a.s3Prev.partials, a.s3Prev.n, n0 ? iterRR0 : nullptr, n0, L);
-                }
-                return gf;
+            [&](bool lm, const LmStep<T>& L) {      // (PRE = false, the pass behind the first launch of the solve: beta's expansion starts from sum r_0^2, which is not the alphaNumerator there)
+                const int n0 = pre || a.afterReset ? 0 : iterRR0n;
+                return launchFlatStep<true>(a, nPad, gf, lm, L, n0 ? iterRR0.p : nullptr, n0, ctx.stream);
             },
             [&](const IterSums<T>& S) {
                 if (pre) return a.CtC ? launchGatherIter<true, true>(a, S, nullptr, ctx) : launchGatherIter<false, true>(a, S, nullptr, ctx);
-                double* rr0 = a.first ? iterRR0 : nullptr;
+                double* rr0 = a.first ? iterRR0.p : nullptr;
                 const int g = a.CtC ? launchGatherIter<true, false>(a, S, rr0, ctx) : launchGatherIter<false, false>(a, S, rr0, ctx);
                 iterRR0n = a.first ? g : 0;
                 return g;

@@ -279,6 +279,20 @@ def without_one_reverse_edge(P, e=5):
     return _with_indices(P, [c[keep] for c in cols])
 
 
+def truncated(P, n):
+    """The first n hyperedges only (n = 1: every vertex list but one or two is empty, and the graph is asymmetric)."""
+    return _with_indices(P, [c[:n] for c in index_arrays(P)])
+
+
+def tetrahedron_with_unused_vertex(energy, double):
+    """The smallest mesh with an EMPTY list between two non-empty ones: 5 vertices, a tetrahedron on {0, 1, 3, 4} (12 half-edges), vertex 2 in no hyperedge.
+    Vertex 0 (smallest x) is the pinned handle, vertex 1 (largest x) the lifted one; vertex 2 lies between them and is neither."""
+    V = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.1], [0.5, 0.4, 0.3], [0.4, 1.0, 0.0], [0.6, 0.5, 1.0]])
+    P = mesh_problem(energy, V, [[0, 1, 3], [0, 4, 1], [1, 4, 3], [0, 3, 4]], double=double, seed=7, perturb=PERTURB[energy])
+    assert n_vertices(P) == 5 and not any(np.any(c == 2) for c in index_arrays(P))
+    return P
+
+
 def max_out_degree(P):
     return int(np.bincount(index_arrays(P)[0], minlength=n_vertices(P)).max())
 

@@ -57,6 +57,14 @@ def _hip_stages(P, v, timing=False):
     return out, t
 
 
+def _as_double(P):
+    """The float problem P for the double oracle: the same float values, widened."""
+    X = P.clone(); X.double = True
+    for s in gc.layout(P)["vertex"]:
+        X.params[s] = X.params[s].astype(np.float64)
+    return X
+
+
 def _check_stages(oracle_lib, P, timing=False):
     """tests/test_energies_gpu.py::test_cost_jtf_diag_jtjp on P; returns the timer table."""
     tol = 1e-11 if P.double else 3e-5
@@ -70,9 +78,7 @@ def _check_stages(oracle_lib, P, timing=False):
     errs = dict(cost=abs(c - c_ref) / abs(c_ref), jtf=rel_err(f, f_ref), diag=rel_err(d, d_ref), jtjv=rel_err(Av, Av_ref))
     print("stages", P.energy, "double" if P.double else "float", {k: f"{e:.3g}" for k, e in errs.items()})
     if not P.double:      # printed, not asserted: how far float arithmetic itself is from the exact value on this input -- the double oracle on the same float arrays
-        X = P.clone(); X.double = True
-        for s in gc.layout(P)["vertex"]:
-            X.params[s] = X.params[s].astype(np.float64)
+        X = _as_double(P)
         ox = oracle_solver(oracle_lib, X)
         fx, dx = ox.eval_jtf(X.params)
         Ax = ox.apply_jtj(X.params, v.astype(np.float64))

@@ -317,16 +317,13 @@ def test_real_cat_mask(oracle_lib, double):
     and PCG amplifies summation-order differences ~30x per iteration (2 iterations: 1e-17 relative in the unknowns, 5: 1e-13,
     40: 1e-4 -- the three-kernel loop, the single-kernel loop and the oracle drift apart at that rate from bit-identical stage
     outputs), so the solve itself is compared in double over one Gauss-Newton step of 5 PCG iterations."""
-    import os
     import torch
-    from opt_amd import io
-    m = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures", "cat_mask_128.npz"))["mask_red"]
-    P = io.image_warping_problem_from_mask(m, downsample=1, double=double)
-    for sx, sy, tx, ty in wl.CAT512_MARKERS:
-        P.params[3][sy // 4, sx // 4] = (tx / 4.0, ty / 4.0)
+    import parity_cases as pc
+    c = pc.real_cat_mask(double)
+    P = c.problem()
     tol = 1e-11 if double else 2e-5
-    o = oracle_solver(oracle_lib, P, nIterations=1, lIterations=5)
-    g = hip_solver(P, nIterations=1, lIterations=5)
+    o = oracle_solver(oracle_lib, P, c.kind, **c.settings())
+    g = hip_solver(P, c.kind, **c.settings())
     dev = api.to_device(P)
     assert abs(g.eval_cost(dev) - o.eval_cost(P.params)) <= (1e-12 if double else 1e-5) * abs(o.eval_cost(P.params))
     f_ref, d_ref = o.eval_jtf(P.params); f_gpu, d_gpu = g.eval_jtf(dev)
@@ -339,7 +336,7 @@ def test_real_cat_mask(oracle_lib, double):
         Pref = P.clone()
         o.init(Pref.params); g.init(dev)
         o.step(Pref.params); g.step(dev)
-        assert_close("cost", g.cost(), o.cost(), 1e-9, double=True)
+        assert_close("cost", g.cost(), o.cost(), 1e-9, double=True, step=1)
         assert_close("x", rel_err(device_unknowns(P, dev), flat_unknowns(Pref)), 0.0, 1e-9, absolute=True, double=True)
     g.close(); o.close()
 

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from opt_amd import api, workloads as wl
+import parity_cases as pc
 from helpers import assert_close, device_unknowns, flat_unknowns, hip_solver, oracle_solver, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -36,7 +37,7 @@ def _side_by_side(oracle_lib, P, nsteps, liters, cost_tol, x_tol, radius_tol, hi
         assert a == b, (a, b, costs)
         costs.append((o.cost(), g.cost()))
         assert_close("cost" if len(costs) <= 2 else "cost_later", g.cost(), o.cost(), cost_tol, floor=1e-12 * scale, double=P.double, step=len(costs) - 1)
-        assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double)
+        assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double, step=len(costs) - 1)
         if not a:
             break
     if x_tol is not None:
@@ -68,29 +69,23 @@ def test_image_warping_double_q_early_out(oracle_lib, period, qtol):
 
 @pytest.mark.parametrize("period,qtol", [(2, None), (3, 0.5), (10, 0.05), (5, 0.0)])
 def test_image_warping_float_controls(oracle_lib, period, qtol):
-    P = wl.image_warping(64, 48, double=False, random_state=9, mask_fraction=0.05, perturb=0.4)
-    kw = dict(residual_reset_period=period)
-    if qtol is not None:
-        kw["q_tolerance"] = qtol
-    _side_by_side(oracle_lib, P, 3, 10, 1e-5, None, 1e-3, **kw)
+    c = pc.lm_controls_image_warping_float(period, qtol)      # (64 x 48 float, 3 x 10)
+    _side_by_side(oracle_lib, c.problem(), c.nsteps, c.liters, 1e-5, None, 1e-3, **c.controls)
 
 
 @pytest.mark.parametrize("double", [True, False])
-@pytest.mark.parametrize("period,qtol,liters", [(1, None, 6), (2, None, 10), (3, None, 12), (3, 0.5, 10), (10, None, 25), (10, 0.05, 12), (4, 0.0, 9), (7, None, 23), (5, 5.0, 10),
-                                                (10, 0.01, 40), (6, 0.002, 60), (10, None, 1), (10, None, 2), (10, None, 3), (2, None, 3), (1, None, 1), (1, None, 2), (3, 5.0, 4)])
+@pytest.mark.parametrize("period,qtol,liters", pc.LAUNCH_LOOP_CONTROLS)
 def test_image_warping_launch_per_iteration_loop_controls(oracle_lib, period, qtol, liters, double):
     """The same controls on the launch-per-iteration LM loop ("amd_onchip" = 0: what images past the on-chip range run on -- the reference's LM-only large-image case,
     examples/image_warping/src/main.cpp:121-129).  Round 6: on a unit lattice that loop keeps no residual vector (ring of three p buffers; true r only behind PCGInit1 and
     behind a reset) and takes Q from the CG recurrence Q_k = Q_{k-1} + alpha_k (p_k . r_k - 1/2 alpha_k p_k . A p_k) instead of summing 1/2 delta . (r + b); a reset
     re-anchors it to the direct sum.  Early-outs on, next to and between resets, restarts, long solves -- step for step beside the oracle, which sums Q directly."""
-    P = wl.image_warping(61, 47, double=double, random_state=5, mask_fraction=0.05, perturb=0.4)
-    kw = dict(residual_reset_period=period)
-    if qtol is not None:
-        kw["q_tolerance"] = qtol
+    c = pc.lm_controls_image_warping_launch_loop(period, qtol, liters, double)      # (61 x 47; 4 outer steps in double, 3 in float)
+    P, kw = c.problem(), c.controls
     if double:
-        _side_by_side(oracle_lib, P, 4, liters, 1e-10, 1e-9, 1e-8, hip_only=dict(amd_onchip=0), **kw)
+        _side_by_side(oracle_lib, P, c.nsteps, c.liters, 1e-10, 1e-9, 1e-8, hip_only=dict(amd_onchip=0), **kw)
     else:
-        _side_by_side(oracle_lib, P, 3, liters, 1e-5, None, 1e-3, hip_only=dict(amd_onchip=0), **kw)
+        _side_by_side(oracle_lib, P, c.nsteps, c.liters, 1e-5, None, 1e-3, hip_only=dict(amd_onchip=0), **kw)
     g = hip_solver(P, "LMGPU", timing=True, nIterations=1, lIterations=liters, amd_onchip=0, **kw)
     dev = api.to_device(P)
     g.init(dev); g.step(dev)
@@ -123,14 +118,12 @@ def test_arap_two_kernel_lm_iteration_controls(oracle_lib, period, qtol, liters,
     """arap_mesh_deformation, Levenberg-Marquardt on the record gather (round 6: arap_flatStepRec<.., LM> + arap_applySym with CtC -- two kernels per PCG iteration where
     the generic loop runs three; reference shape: examples/arap_mesh_deformation/src/main.cpp:81-99): CtC in the gather, b / Q / deltaOut in the flat pass, the restart
     launch after a split residual reset, early-outs on and next to a reset iteration.  The two-kernel loop must actually be the one that ran (kernel names)."""
-    P = wl.arap_mesh_deformation(36, 29, double=double, perturb=0.01)
-    kw = dict(residual_reset_period=period)
-    if qtol is not None:
-        kw["q_tolerance"] = qtol
+    c = pc.lm_controls_arap(period, qtol, liters, double)      # (36 x 29 mesh; 4 outer steps in double, 3 in float)
+    P = c.problem()
     if double:
-        _side_by_side(oracle_lib, P, 4, liters, 1e-10, 1e-9, 1e-8, **kw)
+        _side_by_side(oracle_lib, P, c.nsteps, c.liters, 1e-10, 1e-9, 1e-8, **c.controls)
     else:
-        _side_by_side(oracle_lib, P, 3, liters, 1e-5, None, 1e-3, **kw)
+        _side_by_side(oracle_lib, P, c.nsteps, c.liters, 1e-5, None, 1e-3, **c.controls)
     g = hip_solver(P, "LMGPU", timing=True, nIterations=1, lIterations=max(liters, 3), residual_reset_period=period)
     dev = api.to_device(P)
     g.init(dev); g.step(dev)

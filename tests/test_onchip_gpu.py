@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from opt_amd import api, workloads as wl
+import parity_cases as pc
 from helpers import assert_close, device_unknowns, flat_unknowns, hip_solver, oracle_solver, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -38,10 +39,12 @@ def _pair(oracle_lib, P, nsteps, liters, cost_tol, x_tol, expect_onchip=True):
     Pref = P.clone()
     o.init(Pref.params); g.init(dev)
     scale = max(abs(o.cost()), 1e-300)
+    step = 0
     while True:
         a, b = o.step(Pref.params), g.step(dev)
         assert a == b
-        assert_close("cost", g.cost(), o.cost(), cost_tol, floor=1e-12 * scale, double=P.double)
+        step += 1
+        assert_close("cost", g.cost(), o.cost(), cost_tol, floor=1e-12 * scale, double=P.double, step=step)
         if not a:
             break
     assert _ran_onchip(g) == expect_onchip, g.kernel_timings().keys()
@@ -176,8 +179,8 @@ def test_too_large_or_general_inputs_take_the_streaming_kernels(oracle_lib):
 
 def test_many_steps_tag_counter_runs_on(oracle_lib):
     """19 x 8 launches of the example flow's shape on one plan: tags never repeat, the double buffers alternate whatever the parity of the counts."""
-    P = wl.image_warping(260, 131, double=True, random_state=21, mask_fraction=0.05, perturb=0.3)
-    _pair(oracle_lib, P, 9, 5, 1e-10, 1e-9)
+    c = pc.onchip_many_steps()      # (260 x 131 double, 9 x 5)
+    _pair(oracle_lib, c.problem(), c.nsteps, c.liters, 1e-10, 1e-9)
 
 
 @pytest.mark.parametrize("fail_launch,nsteps", [(0, 4), (2, 6), (3, 12), (7, 12), (9, 12), (5, 6)])
@@ -188,16 +191,17 @@ def test_a_time_out_among_deferred_steps_sends_the_solve_back_to_that_step(oracl
     the oracle, whatever the position of the failure in the window (first step, middle, the step that drains the window, the last step of the solve)."""
     monkeypatch.setenv("OPT_AMD_ONCHIP_FAIL_AT", "3")
     monkeypatch.setenv("OPT_AMD_ONCHIP_FAIL_LAUNCH", str(fail_launch))
-    P = wl.image_warping(300, 120, double=True, random_state=4, mask_fraction=0.05, perturb=0.3)
-    o = oracle_solver(oracle_lib, P, "gaussNewtonGPU", nIterations=nsteps, lIterations=8)
+    c = pc.onchip_deferred_time_out(nsteps)      # (300 x 120 double, nsteps x 8)
+    P = c.problem()
+    o = oracle_solver(oracle_lib, P, c.kind, **c.settings())
     Pref = P.clone()
     o.solve(Pref.params)
-    g = hip_solver(P, "gaussNewtonGPU", timing=True, nIterations=nsteps, lIterations=8)
+    g = hip_solver(P, c.kind, timing=True, **c.settings())
     dev = api.to_device(P)
     g.solve(dev)
     t = g.kernel_timings()
     assert "PCGIteration" in t and "PCGSolveOnChip" in t, t.keys()
-    assert_close("cost", g.cost(), o.cost(), 1e-10, double=True)
+    assert_close("cost", g.cost(), o.cost(), 1e-10, double=True, step=nsteps)
     assert_close("x", rel_err(device_unknowns(P, dev), flat_unknowns(Pref)), 0.0, 1e-9, absolute=True, double=True)
     assert "timed out" in capfd.readouterr().err
     g.close(); o.close()

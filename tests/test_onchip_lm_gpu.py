@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from opt_amd import api, workloads as wl
+import parity_cases as pc
 from helpers import assert_close, device_unknowns, flat_unknowns, hip_solver, oracle_solver, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +42,7 @@ def _side_by_side(oracle_lib, P, nsteps, liters, cost_tol, x_tol, radius_tol, ex
         tol = cost_tol if (later_tol is None or len(costs) <= 2) else later_tol      # later_tol: outer steps after the first (float runs, see test_variants_float)
         assert_close("cost" if len(costs) <= 2 else "cost_later", g.cost(), o.cost(), tol, floor=1e-12 * scale, double=P.double, step=len(costs) - 1)
         if later_tol is None or len(costs) <= 2:
-            assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double)
+            assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double, step=len(costs) - 1)
         if not a:
             break
     assert _ran_onchip(g) == expect_onchip, g.kernel_timings().keys()
@@ -58,8 +59,8 @@ SHAPES = [(96, 64), (300, 40), (517, 33), (64, 300), (260, 131), (1, 70), (700, 
 @pytest.mark.parametrize("liters,period", [(9, 10), (10, 10), (10, 3), (12, 5), (7, 1), (12, 2)])
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_double(oracle_lib, W, H, liters, period):
-    P = wl.image_warping(W, H, double=True, random_state=W * 13 + H + liters + period, mask_fraction=0.1, perturb=0.4)
-    _side_by_side(oracle_lib, P, 3, liters, 1e-10, 1e-9, 1e-8, residual_reset_period=period)
+    c = pc.onchip_lm_double(W, H, liters, period)      # (random_state = 13 W + H + liters + period; 3 outer steps)
+    _side_by_side(oracle_lib, c.problem(), c.nsteps, c.liters, 1e-10, 1e-9, 1e-8, threads=c.threads, **c.controls)
 
 
 @pytest.mark.parametrize("liters,period", [(10, 10), (12, 5), (25, 10), (9, 2)])
@@ -67,7 +68,7 @@ def test_double(oracle_lib, W, H, liters, period):
 @pytest.mark.parametrize("W,H", [s for s in SHAPES if s != (700, 3)])      # (700 x 3 in float: its later outer steps drift 3e-3 from the oracle, the streaming HIP loop likewise; the shape is pinned in double, test_double)
 def test_variants_float(oracle_lib, monkeypatch, W, H, rows, liters, period):
     monkeypatch.setenv("OPT_AMD_ONCHIP_ROWS", str(rows))
-    P = wl.image_warping(W, H, random_state=W * 7 + H + rows + liters, mask_fraction=0.1, perturb=0.4)
+    c = pc.onchip_lm_variants_float(W, H, rows, liters, period)      # (random_state = 7 W + H + rows + liters; 3 outer steps; q_tolerance = -1e9)
     # q_tolerance = -1e9 (never: 0 would still break on a NEGATIVE zeta, which in float happens behind a residual reset when Q is not monotone to the last bit -- 257 x 9,
     # 25 iterations): in float the zeta test can sit on a knife's edge (517 x 33, period 2: zeta = 0.996e-4 against 1e-4 at k = 6, with Q = 1.3e6 known to
     # 0.125 -- the oracle breaks, every HIP loop, streaming or on chip, goes on: 1.6 % in the cost); the decisions themselves are pinned in double
@@ -75,7 +76,7 @@ def test_variants_float(oracle_lib, monkeypatch, W, H, rows, liters, period):
     # The first outer step holds the float contract (1e-5).  The steps after it start from unknowns that already differ in their last bits and run another
     # undamped-enough linear solve on them: 700 x 3, period 5 ends its second step 2e-4 from the oracle in float while the same case in double agrees to 1e-10
     # (test_double) -- those steps check the hand-over of the loop state between launches (phase tags, trust region), at 1e-3.
-    _side_by_side(oracle_lib, P, 3, liters, 1e-5, None, 1e-3, residual_reset_period=period, q_tolerance=-1e9, later_tol=1e-3)
+    _side_by_side(oracle_lib, c.problem(), c.nsteps, c.liters, 1e-5, None, 1e-3, threads=c.threads, later_tol=1e-3, **c.controls)
 
 
 @pytest.mark.parametrize("qtol", [None, 0.0, 0.05, 0.5, 5.0])

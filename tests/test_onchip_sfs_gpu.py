@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from opt_amd import api, workloads as wl
+import parity_cases as pc
 from helpers import assert_close, device_unknowns, flat_unknowns, hip_solver, oracle_solver, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -27,9 +28,9 @@ def _ran_onchip(g):
     return "PCGSolveOnChip" in g.kernel_timings()
 
 
-def _side_by_side(oracle_lib, P, kind, nsteps, liters, cost_tol, x_tol, radius_tol=None, expect_onchip=True, status=None, later_tol=None, **controls):
+def _side_by_side(oracle_lib, P, kind, nsteps, liters, cost_tol, x_tol, radius_tol=None, expect_onchip=True, status=None, later_tol=None, threads=4, **controls):
     o = oracle_solver(oracle_lib, P, kind, nIterations=nsteps, lIterations=liters, **controls)
-    o.set_threads(4)
+    o.set_threads(threads)
     g = hip_solver(P, kind, timing=True, nIterations=nsteps, lIterations=liters, **controls)
     dev = api.to_device(P)
     Pref = P.clone()
@@ -43,7 +44,7 @@ def _side_by_side(oracle_lib, P, kind, nsteps, liters, cost_tol, x_tol, radius_t
         tol = cost_tol if (later_tol is None or len(costs) <= 2) else later_tol
         assert_close("cost" if len(costs) <= 2 else "cost_later", g.cost(), o.cost(), tol, floor=1e-12 * scale, double=P.double, step=len(costs) - 1)
         if radius_tol is not None and (later_tol is None or len(costs) <= 2):
-            assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double)
+            assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double, step=len(costs) - 1)
         if not a:
             break
     assert _ran_onchip(g) == expect_onchip, g.kernel_timings().keys()
@@ -65,13 +66,14 @@ ROWS = [4, 6, 8, 10]
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_variants_double(oracle_lib, monkeypatch, W, H, rows, waves, kind):
     monkeypatch.setenv("OPT_AMD_ONCHIP_ROWS", str(rows)); monkeypatch.setenv("OPT_AMD_ONCHIP_WAVES", str(waves))
-    P = wl.shape_from_shading(W, H, double=True, seed=W + 3 * H + rows, holes=True, noise=2e-3)
+    c = pc.sfs_variants_double(W, H, rows, kind)      # (seed = W + 3 H + rows; 3 x 10, the oracle on 4 threads)
     # the first outer step at the contract; the steps after it start from unknowns that differ in their last bits and drive the cost down by orders of magnitude
     # (5 x 70 GN: 2.4 -> 0.087 -> 0.070, 4.5e-10 apart after the third step, the marching kernels likewise): 1e-8
     # (Gauss-Newton on an image a few pixels thin -- 123 x 4, 5 x 70: an undamped, ill-conditioned normal matrix -- turns the last bits of the sums into 3e-9 of the
-    # cost after ten iterations; the damped LM step of the same images holds 1e-10)
+    # cost after ten iterations; the damped LM step of the same images holds 1e-10).  These are only the defaults: the thin-image parametrisations have entries in
+    # tests/golden/parity_bars.json, twice the spread of the oracle's own legal runs of the same case at the same step (123 x 4, rows 4: 4.9e-9 after the first step)
     thin = min(W, H) <= 5 and kind == "gaussNewtonGPU"
-    _side_by_side(oracle_lib, P, kind, 3, 10, 1e-8 if thin else 1e-10, 1e-7, 1e-8 if kind == "LMGPU" else None, later_tol=1e-8)
+    _side_by_side(oracle_lib, c.problem(), c.kind, c.nsteps, c.liters, 1e-8 if thin else 1e-10, 1e-7, 1e-8 if kind == "LMGPU" else None, later_tol=1e-8, threads=c.threads, **c.controls)
 
 
 @pytest.mark.parametrize("kind", ["gaussNewtonGPU", "LMGPU"])
@@ -80,9 +82,9 @@ def test_variants_double(oracle_lib, monkeypatch, W, H, rows, waves, kind):
 @pytest.mark.parametrize("W,H", [(40, 32), (130, 37), (200, 150)])
 def test_variants_float(oracle_lib, monkeypatch, W, H, rows, waves, kind):
     monkeypatch.setenv("OPT_AMD_ONCHIP_ROWS", str(rows)); monkeypatch.setenv("OPT_AMD_ONCHIP_WAVES", str(waves))
-    P = wl.shape_from_shading(W, H, double=False, seed=W + H + rows, holes=True, noise=2e-3)
+    c = pc.sfs_variants_float(W, H, rows, kind)      # (seed = W + H + rows; 2 x 10; LM with q_tolerance = -1e9: never)
     # the first outer step holds the float contract; later steps start from unknowns that already differ in their last bits (see test_onchip_lm_gpu.py)
-    _side_by_side(oracle_lib, P, kind, 2, 10, 1e-5, None, 1e-3 if kind == "LMGPU" else None, later_tol=1e-3, **({"q_tolerance": -1e9} if kind == "LMGPU" else {}))
+    _side_by_side(oracle_lib, c.problem(), c.kind, c.nsteps, c.liters, 1e-5, None, 1e-3 if kind == "LMGPU" else None, later_tol=1e-3, threads=c.threads, **c.controls)
 
 
 @pytest.mark.parametrize("liters", [1, 2, 3, 7])
@@ -107,8 +109,8 @@ def test_lm_q_early_out_double(oracle_lib, qtol):
 
 def test_lm_rejected_steps(oracle_lib):
     """a trust region far too large: the first steps are rejected (unknowns restored, radius shrinks), the on-chip solve runs again on the same plan"""
-    P = wl.shape_from_shading(96, 64, double=True, seed=5, noise=5e-3)
-    _side_by_side(oracle_lib, P, "LMGPU", 6, 10, 1e-10, 1e-9, 1e-8, trust_region_radius=1e12)
+    c = pc.sfs_lm_rejected_steps()      # (96 x 64, 6 x 10, trust_region_radius = 1e12)
+    _side_by_side(oracle_lib, c.problem(), c.kind, c.nsteps, c.liters, 1e-10, 1e-9, 1e-8, threads=c.threads, **c.controls)
 
 
 @pytest.mark.parametrize("kind", ["gaussNewtonGPU", "LMGPU"])

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from opt_amd import api, workloads as wl
+import parity_cases as pc
 from helpers import assert_close, device_unknowns, flat_unknowns, hip_solver, oracle_solver, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -22,15 +23,7 @@ SHAPES = [(1, 1), (1, 7), (7, 1), (2, 2), (61, 5), (62, 3), (63, 9), (300, 40), 
 VARIANTS = [(2, 4), (4, 4), (8, 4), (2, 8), (4, 8), (8, 8)]
 
 
-def _poisson(W, H, double, seed, mask):
-    P = wl.poisson_image_editing(W, H, double=double, seed=seed)
-    rng = np.random.default_rng(seed + 100)
-    M = P.params[2]
-    if mask == "random":
-        M[...] = np.where(rng.random(M.shape) < 0.3, 255.0, 0.0)
-    elif mask == "none":
-        M[...] = 0.0
-    return P
+_poisson = pc.masked_poisson
 
 
 def _cap(W, H, liters, double=True):
@@ -46,10 +39,12 @@ def _pair(oracle_lib, P, nsteps, liters, cost_tol, x_tol, status=1):
     Pref = P.clone()
     o.init(Pref.params); g.init(dev)
     scale = max(abs(o.cost()), 1e-300)
+    step = 0
     while True:
         a, b = o.step(Pref.params), g.step(dev)
         assert a == b
-        assert_close("cost", g.cost(), o.cost(), cost_tol, floor=1e-9 * scale, double=P.double)
+        step += 1
+        assert_close("cost", g.cost(), o.cost(), cost_tol, floor=1e-9 * scale, double=P.double, step=step)
         if not a:
             break
     kt = g.kernel_timings()
@@ -133,9 +128,9 @@ def test_config1_poisson_256_takes_the_onchip_solve(oracle_lib):
 
 
 # ---- Levenberg-Marquardt (march_onchipPcg<.., LM = true>): CtC, Q with the next iteration's sums, the early-out decided on chip ------------------------------------
-def _lm_side_by_side(oracle_lib, P, nsteps, liters, cost_tol, x_tol, radius_tol, expect_onchip=True, status=None, later_tol=None, **controls):
+def _lm_side_by_side(oracle_lib, P, nsteps, liters, cost_tol, x_tol, radius_tol, expect_onchip=True, status=None, later_tol=None, threads=4, **controls):
     o = oracle_solver(oracle_lib, P, "LMGPU", nIterations=nsteps, lIterations=liters, **controls)
-    o.set_threads(4)
+    o.set_threads(threads)
     g = hip_solver(P, "LMGPU", timing=True, nIterations=nsteps, lIterations=liters, **controls)
     dev = api.to_device(P)
     Pref = P.clone()
@@ -149,7 +144,7 @@ def _lm_side_by_side(oracle_lib, P, nsteps, liters, cost_tol, x_tol, radius_tol,
         tol = cost_tol if (later_tol is None or len(costs) <= 2) else later_tol
         assert_close("cost" if len(costs) <= 2 else "cost_later", g.cost(), o.cost(), tol, floor=1e-9 * scale, double=P.double, step=len(costs) - 1)
         if later_tol is None or len(costs) <= 2:
-            assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double)
+            assert_close("radius", g.trust_region_radius(), o.trust_region_radius(), radius_tol, double=P.double, step=len(costs) - 1)
         if not a:
             break
     assert ("PCGSolveOnChip" in g.kernel_timings()) == expect_onchip, g.kernel_timings().keys()
@@ -167,7 +162,8 @@ LM_SHAPES = [(7, 9), (61, 5), (62, 3), (63, 9), (300, 40), (64, 300), (517, 33)]
 @pytest.mark.parametrize("W,H", LM_SHAPES)
 def test_lm_poisson_double(oracle_lib, monkeypatch, W, H, mask, rows, waves):
     monkeypatch.setenv("OPT_AMD_ONCHIP_ROWS", str(rows)); monkeypatch.setenv("OPT_AMD_ONCHIP_WAVES", str(waves))
-    _lm_side_by_side(oracle_lib, _poisson(W, H, True, W * 3 + H, mask), 3, 10, 1e-10, 1e-9, 1e-8)
+    c = pc.stencil_lm_poisson_double(W, H, mask)      # (seed = 3 W + H; 3 x 10, the oracle on 4 threads)
+    _lm_side_by_side(oracle_lib, c.problem(), c.nsteps, c.liters, 1e-10, 1e-9, 1e-8, threads=c.threads, **c.controls)
 
 
 @pytest.mark.parametrize("rows,waves", VARIANTS)
@@ -215,7 +211,8 @@ def test_lm_timeout_path(oracle_lib, monkeypatch, fail_at):
 def test_intrinsic_double(oracle_lib, monkeypatch, W, H, rows, waves, liters):
     """(ill-conditioned, unpreconditioned: 1e-8 / 1e-7 as in tests/test_stencil_march_gpu.py)"""
     monkeypatch.setenv("OPT_AMD_ONCHIP_ROWS", str(rows)); monkeypatch.setenv("OPT_AMD_ONCHIP_WAVES", str(waves))
-    _pair(oracle_lib, wl.intrinsic_image_decomposition(W, H, double=True, seed=W + H + liters), 2, liters, 1e-8, 1e-7)
+    c = pc.stencil_intrinsic_double(W, H, liters)      # (seed = W + H + liters; 2 Gauss-Newton steps)
+    _pair(oracle_lib, c.problem(), c.nsteps, c.liters, 1e-8, 1e-7)
 
 
 @pytest.mark.parametrize("rows,waves", VARIANTS)

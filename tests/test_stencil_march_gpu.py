@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from opt_amd import api, workloads as wl
+import parity_cases as pc
 from helpers import assert_close, device_unknowns, flat_unknowns, hip_solver, oracle_solver, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -23,15 +24,7 @@ def _marching_kernels_only(monkeypatch):
 SHAPES = [(1, 1), (1, 7), (7, 1), (2, 2), (61, 5), (240, 3), (241, 9), (300, 40), (64, 300), (517, 33)]
 
 
-def _poisson(W, H, double, seed, mask):
-    P = wl.poisson_image_editing(W, H, double=double, seed=seed)
-    rng = np.random.default_rng(seed + 100)
-    M = P.params[2]
-    if mask == "random":
-        M[...] = np.where(rng.random(M.shape) < 0.3, 255.0, 0.0)
-    elif mask == "none":
-        M[...] = 0.0
-    return P
+_poisson = pc.masked_poisson
 
 
 def _cap(W, H, liters, double=True):
@@ -48,10 +41,12 @@ def _pair(oracle_lib, P, nsteps, liters, cost_tol, x_tol):
     Pref = P.clone()
     o.init(Pref.params); g.init(dev)
     scale = max(abs(o.cost()), 1e-300)
+    step = 0
     while True:
         a, b = o.step(Pref.params), g.step(dev)
         assert a == b
-        assert_close("cost", g.cost(), o.cost(), cost_tol, floor=1e-9 * scale, double=P.double)
+        step += 1
+        assert_close("cost", g.cost(), o.cost(), cost_tol, floor=1e-9 * scale, double=P.double, step=step)
         if not a:
             break
     assert "PCGIteration" in g.kernel_timings() and "PCGStep1" not in g.kernel_timings()
@@ -93,10 +88,11 @@ def test_optical_flow(oracle_lib, W, H, double, liters):
 @pytest.mark.parametrize("W,H", [(7, 9), (61, 5), (240, 3), (241, 9), (300, 40), (64, 300), (517, 33)])
 def test_intrinsic_double(oracle_lib, W, H, liters):
     """intrinsic_image_decomposition: two unknown images (3 + 1 channels per pixel, the template's split layout) and four L_p weights per pixel as operator coefficients.
-    The system is ill-conditioned (weights 500 / 1000 / 10000 on differences of ~0.02, unpreconditioned): a 1-ulp difference between libm pow and the device pow is
-    amplified ~1e7-fold in a Gauss-Newton step, which is why the double bars are 1e-8 / 1e-7 here as in tests/test_energies_gpu.py; float runs are smoke level there."""
-    P = wl.intrinsic_image_decomposition(W, H, double=True, seed=W + H + liters)
-    _pair(oracle_lib, P, 2, liters, 1e-8, 1e-7)
+    The system is ill-conditioned (weights 500 / 1000 / 10000 on differences of ~0.02, unpreconditioned): sum order and fused multiply-adds alone move the oracle's own
+    legal runs up to 1.4e-9 apart after two Gauss-Newton steps (tests/golden/parity_envelopes.json), so the parametrisations above 1e-12 are held to twice that spread per
+    case (tests/golden/parity_bars.json; the 1e-8 / 1e-7 below are only the defaults of a parametrisation without an entry); float runs are smoke level there."""
+    c = pc.stencil_intrinsic_double(W, H, liters)      # (seed = W + H + liters; 2 Gauss-Newton steps)
+    _pair(oracle_lib, c.problem(), c.nsteps, c.liters, 1e-8, 1e-7)
 
 
 def test_intrinsic_march_matches_the_functor_engine_loop(monkeypatch):

@@ -4,6 +4,9 @@
  * (or several) without rebuilding the library: a shared object that holds the energy's kernels and hands libOpt.so a registry entry per energy.
  * After OptAmd_LoadEnergyPlugin (OptAmd.h; or OPT_AMD_ENERGY_PLUGINS) the energy's .t file is planned, probed and solved through the unmodified Opt_* API.
  * This header is C++ (HIP): it is what a plug-in SOURCE includes, never what a caller of the library includes.
+ * Such a source can be generated: opt_amd/tgen.py translates a .t of a documented subset of the DSL into one in the shape of the two worked examples (the functor,
+ * its tables, the ParamDecls, the body hash), `python -m opt_amd.tgen my_energy.t` builds it.  What follows is the contract
+ * such a source -- written or generated -- meets.
  *
  * A plug-in source for a MESH energy is (examples/plugins/spring_mesh_deformation.hip is the worked example; compile it with opt_amd/build.py build_plugin):
  *

@@ -107,6 +107,16 @@ def load_energy_plugin(path):
     return n
 
 
+def compile_and_load_energy(t_path, force=True):
+    """From a .t alone (opt_amd/tgen.py: the documented DSL subset): generate the plug-in source, build it for gfx950 and register it for the rest of the process.
+    The energy's name is the .t stem; returns the library path.  Raises tgen.TgenError for a .t outside the subset, RuntimeError if the loader refuses the library
+    (a name that is already registered, for one)."""
+    from . import tgen
+    path = tgen.compile_energy(t_path, force=force)
+    load_energy_plugin(path)
+    return path
+
+
 def problem_file_hash(path):
     """Body hash of a .t file (OptAmd_ProblemFileHash): what a plug-in records in EnergyInfo::bodyHashes.  0 if the file cannot be read."""
     return lib().OptAmd_ProblemFileHash(os.fsencode(path))
